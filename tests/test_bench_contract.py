@@ -59,6 +59,73 @@ def test_bench_json_contract():
     assert cfg["model"] == "dra-claim-lifecycle/whole"
     assert cfg["hal"] in ("fake", "amdsmi")
     assert cfg["alloc_prepare_p50_ms"] > 0
+    # a plain run measures the headline only; the rest is behind --full
+    assert "configs" not in cfg
+    assert cfg["cpus"]  # the L3 domain it pinned itself to, or "unpinned"
+
+
+def test_bench_cpu_list_parsing_and_pinning():
+    sys.path.insert(0, REPO)
+    import bench
+
+    assert bench._parse_cpu_list("16-23,144-151\n") == set(range(16, 24)) | set(
+        range(144, 152)
+    )
+    assert bench._parse_cpu_list("3") == {3}
+    before = os.sched_getaffinity(0)
+    try:
+        pinned = bench.pin_to_one_l3()
+        after = os.sched_getaffinity(0)
+        if pinned:
+            assert after < before
+            assert after == bench._parse_cpu_list(pinned) & before
+        else:
+            assert after == before
+    finally:
+        for tid in os.listdir("/proc/self/task"):
+            os.sched_setaffinity(int(tid), before)
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last step's allocation results + prepare
+    responses as float arrays, identical from run to run."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        out = subprocess.run(
+            [
+                sys.executable,
+                os.path.join(REPO, "bench.py"),
+                "--steps", "2", "--warmup", "1", "--pods-per-step", "4",
+                "--hal", "fake",
+                "--dump-outputs", str(tmp_path / name),
+            ],
+            capture_output=True,
+            text=True,
+            cwd=REPO,
+            timeout=280,
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["lifecycle_results.npy", "prepared_device_counts.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    for f in a:
+        assert a[f].dtype == np.float32
+        assert np.array_equal(a[f], b[f]), f
+    # one record per lifecycle of the last step, each with its one device
+    assert a["prepared_device_counts.npy"].tolist() == [1.0] * 4
+    rows = a["lifecycle_results.npy"]
+    assert rows.shape[0] == 4
+    rec = json.loads(bytes(rows[0].astype("uint8")).rstrip(b"\0"))
+    (uid,) = rec["allocation"]
+    assert rec["allocation"][uid][0]["device"] == "gpu-0"
+    dev = rec["prepared"][uid][0]
+    assert dev["device_name"] == "gpu-0"
+    assert dev["pool_name"] == "bench-node-0"
+    assert len(dev["cdi_device_ids"]) == 2
 
 
 def test_metrics_histograms():
@@ -139,13 +206,13 @@ def test_repartition_metric_counts(tmp_path):
 
 def test_bench_all_configs_attested():
     """BASELINE configs #1-#5 are first-class bench modes:
-    --config all emits the whole-GPU headline plus per-config results."""
+    --full emits the whole-GPU headline plus per-config results."""
     out = subprocess.run(
         [
             sys.executable,
             os.path.join(REPO, "bench.py"),
             "--steps", "2", "--warmup", "1", "--pods-per-step", "8",
-            "--config", "all",
+            "--full",
         ],
         capture_output=True,
         text=True,

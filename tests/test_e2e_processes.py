@@ -39,10 +39,10 @@ def api(tmp_path):
 
 
 @pytest.mark.timeout(120)
-def test_plugin_process_end_to_end(api, tmp_path):
+def test_plugin_process_end_to_end(api, tmp_path, sock_dir):
     srv, kubeconfig = api
-    plugin_dir = tmp_path / "plugins" / DRIVER_NAME
-    registry_dir = tmp_path / "plugins_registry"
+    plugin_dir = sock_dir / "plugins" / DRIVER_NAME
+    registry_dir = sock_dir / "plugins_registry"
     env = dict(
         os.environ,
         PYTHONPATH=REPO,
@@ -209,7 +209,7 @@ def _make_pki(d):
 
 
 @pytest.mark.timeout(120)
-def test_plugin_process_mtls_apiserver(tmp_path):
+def test_plugin_process_mtls_apiserver(tmp_path, sock_dir):
     """The round-1 gap closed end to end: the REAL plugin
     binary connects to an apiserver that REQUIRES a client certificate,
     using a kind-style kubeconfig with inline cert data, then registers,
@@ -232,8 +232,8 @@ def test_plugin_process_mtls_apiserver(tmp_path):
         client_cert=str(pki / "client.crt"),
         client_key=str(pki / "client.key"),
     )
-    plugin_dir = tmp_path / "plugins" / DRIVER_NAME
-    registry_dir = tmp_path / "plugins_registry"
+    plugin_dir = sock_dir / "plugins" / DRIVER_NAME
+    registry_dir = sock_dir / "plugins_registry"
     env = dict(
         os.environ, PYTHONPATH=REPO, NODE_NAME="e2e-node", KUBECONFIG=kubeconfig
     )
@@ -287,6 +287,8 @@ def test_plugin_process_mtls_apiserver(tmp_path):
         )
         m = V1BETA1
         reg_sock = registry_dir / f"{DRIVER_NAME}.sock"
+        # slices can be published before the gRPC server has bound
+        _wait_for(reg_sock.exists, what="registration socket")
         reg_channel = grpc.insecure_channel(f"unix://{reg_sock}")
         info = reg_channel.unary_unary(
             f"/{REGISTRATION.service_name}/GetInfo",
@@ -317,7 +319,7 @@ def test_plugin_process_mtls_apiserver(tmp_path):
 
 
 @pytest.mark.timeout(90)
-def test_plugin_process_publishes_v1beta2(tmp_path):
+def test_plugin_process_publishes_v1beta2(tmp_path, sock_dir):
     """Real plugin binary against an apiserver preferring v1beta2: the
     published slices carry the flattened Device shape + counters when
     prospective partitioning is on."""
@@ -339,8 +341,8 @@ def test_plugin_process_publishes_v1beta2(tmp_path):
             "--hal", "fake",
             "--prospective-partitions", "cpx",
             "--cdi-root", str(tmp_path / "cdi"),
-            "--plugin-path", str(tmp_path / "plugins" / DRIVER_NAME),
-            "--plugin-registration-path", str(tmp_path / "plugins_registry"),
+            "--plugin-path", str(sock_dir / "plugins" / DRIVER_NAME),
+            "--plugin-registration-path", str(sock_dir / "plugins_registry"),
         ],
         env=env,
         cwd=REPO,

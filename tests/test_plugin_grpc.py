@@ -19,7 +19,7 @@ NODE = "node-a"
 
 
 @pytest.fixture
-def stack(tmp_path):
+def stack(tmp_path, sock_dir):
     lib = FakeDeviceLib()
     lib.open()
     kube = InMemoryKube()
@@ -34,8 +34,8 @@ def stack(tmp_path):
     driver.startup()
     server = PluginServer(
         driver,
-        plugin_dir=str(tmp_path / "plugins" / DRIVER_NAME),
-        registry_dir=str(tmp_path / "plugins_registry"),
+        plugin_dir=str(sock_dir / "plugins" / DRIVER_NAME),
+        registry_dir=str(sock_dir / "plugins_registry"),
     )
     server.start()
     channel = grpc.insecure_channel(f"unix://{server.plugin_sock}")

@@ -11,7 +11,7 @@ from k8s_dra_driver_amd.plugin.proto import V1BETA1
 from k8s_dra_driver_amd.plugin.server import PluginServer
 
 
-def make_server(tmp_path):
+def make_server(tmp_path, sock_dir=None):
     lib = FakeDeviceLib()
     lib.open()
     driver = Driver(
@@ -23,15 +23,17 @@ def make_server(tmp_path):
         use_tmpfs=False,
     )
     driver.startup()
-    return PluginServer(driver, plugin_dir=str(tmp_path / "plugin"))
+    return PluginServer(
+        driver, plugin_dir=str((sock_dir or tmp_path) / "plugin")
+    )
 
 
 def test_stop_without_start_is_safe(tmp_path):
     make_server(tmp_path).stop()
 
 
-def test_restart_reuses_socket_path(tmp_path):
-    server = make_server(tmp_path)
+def test_restart_reuses_socket_path(tmp_path, sock_dir):
+    server = make_server(tmp_path, sock_dir)
     server.start()
     sock = server.plugin_sock
     server.stop()
@@ -52,8 +54,8 @@ def test_restart_reuses_socket_path(tmp_path):
     server.stop()
 
 
-def test_double_stop_idempotent(tmp_path):
-    server = make_server(tmp_path)
+def test_double_stop_idempotent(tmp_path, sock_dir):
+    server = make_server(tmp_path, sock_dir)
     server.start()
     server.stop()
     server.stop()
