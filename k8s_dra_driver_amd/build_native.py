@@ -4,6 +4,8 @@ in the package directory so they travel with the source tree).
 - ``_amdhal``: plain C++ (g++/amdclang++), links libamd_smi.
 - ``_hiphealth``: HIP, compiled for gfx950 only (hipcc cross-compiles
   without a GPU present).
+- ``_claimio``: plain C++, no external link; the prepare path's JSON
+  encoding, checksum and atomic file writes.
 """
 
 from __future__ import annotations
@@ -117,9 +119,71 @@ def build_hiphealth(force: bool = False) -> str:
     return out
 
 
+def build_claimio(force: bool = False) -> str:
+    """Claim persistence (JSON encode + checksum + atomic write); plain
+    C++, no ROCm link. Rebuilt when either the binding or its Python-free
+    core header changes."""
+    src = os.path.join(CPP_DIR, "claimio.cpp")
+    hdr = os.path.join(CPP_DIR, "claimio_core.hpp")
+    out = os.path.join(PKG_DIR, f"_claimio{_ext_suffix()}")
+    if force or _needs_build(src, out) or _needs_build(hdr, out):
+        _run(
+            ["g++", "-shared", "-fPIC", "-O2", "-std=c++17"]
+            + _pybind_includes()
+            + [src, "-o", out]
+        )
+    return out
+
+
+def _gcc_file(name: str) -> str:
+    """Absolute path of a gcc support file, "" when it is not installed."""
+    try:
+        out = subprocess.run(
+            ["gcc", f"-print-file-name={name}"],
+            capture_output=True,
+            text=True,
+            check=True,
+        ).stdout.strip()
+    except (OSError, subprocess.CalledProcessError):
+        return ""
+    return out if os.path.isabs(out) else ""
+
+
+def sanitizer_link_flags():
+    """Link flags for an ASan+UBSan executable, or None when gcc has no
+    sanitizer runtime installed. The static runtimes are preferred: the
+    program then carries its sanitizer with it and does not depend on the
+    order in which shared libraries are loaded into the process."""
+    if _gcc_file("libasan.a") and _gcc_file("libubsan.a"):
+        return ["-static-libasan", "-static-libubsan"]
+    if _gcc_file("libasan.so") and _gcc_file("libubsan.so"):
+        return []
+    return None
+
+
+def build_claimio_selftest(out: str, sanitize: bool = True) -> str:
+    """Stand-alone driver of claimio_core.hpp (its own ``main``, no
+    Python), by default under AddressSanitizer + UBSan. CPU only; run the
+    binary directly."""
+    src = os.path.join(CPP_DIR, "claimio_selftest.cpp")
+    flags = ["-g", "-O1", "-std=c++17"]
+    if sanitize:
+        link = sanitizer_link_flags()
+        if link is None:
+            raise RuntimeError("gcc has no ASan/UBSan runtime installed")
+        flags += [
+            "-fsanitize=address,undefined",
+            "-fno-sanitize-recover=undefined",
+            "-fno-omit-frame-pointer",
+        ] + link
+    _run(["g++"] + flags + [src, "-o", out])
+    return out
+
+
 def build(force: bool = False) -> None:
     build_amdhal(force)
     build_hiphealth(force)
+    build_claimio(force)
 
 
 if __name__ == "__main__":

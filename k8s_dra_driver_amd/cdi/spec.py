@@ -152,14 +152,15 @@ def write_spec_file(spec: CDISpec, path: str, *, durable: bool = True) -> None:
     (cdi.go:225-227); writing directly keeps the hot path to one syscall
     sequence. Per-claim specs pass ``durable=False``: they are regenerated
     from the (fsynced) checkpoint after a crash, so rename atomicity is
-    the only requirement."""
-    from ..utils.atomicfile import atomic_write_text
+    the only requirement.
 
-    atomic_write_text(
-        path,
-        json.dumps(spec.to_json(), indent=2, sort_keys=True),
-        durable=durable,
-    )
+    The bytes are those of ``json.dumps(spec.to_json(), indent=2,
+    sort_keys=True)``; ``encode_json`` produces them natively when the
+    ``_claimio`` extension is loaded (any ``indent`` forces json's
+    pure-Python encoder, the single most expensive step of a prepare)."""
+    from ..utils.atomicfile import atomic_write_bytes, encode_json
+
+    atomic_write_bytes(path, encode_json(spec.to_json(), 2), durable=durable)
 
 
 def read_spec_file(path: str) -> dict:

@@ -23,6 +23,7 @@ import zlib
 from dataclasses import asdict, dataclass, field
 from typing import Dict, List, Optional
 
+from ..utils import atomicfile
 from ..utils.atomicfile import atomic_write_json, read_json
 
 
@@ -115,15 +116,29 @@ class CheckpointStore:
     SCHEMA_VERSION = 1
 
     def write(self, claim: PreparedClaim) -> None:
-        v1 = claim.to_v1()
-        atomic_write_json(
-            self._path(claim.claim_uid),
-            {
-                "version": self.SCHEMA_VERSION,
-                "checksum": _checksum(v1),
-                "v1": v1,
-            },
-        )
+        path = self._path(claim.claim_uid)
+        data = None
+        nat = atomicfile.native()
+        if nat is not None:
+            # one native pass over the live dataclass: payload, CRC and
+            # wrapper, byte-identical to the three Python passes below
+            # (asdict, checksum dump, file dump)
+            try:
+                data = nat.encode_checkpoint(claim, self.SCHEMA_VERSION)
+            except TypeError:
+                data = None  # a value only json.dumps renders (e.g. float)
+        if data is not None:
+            atomicfile.atomic_write_bytes(path, data)
+        else:
+            v1 = claim.to_v1()
+            atomic_write_json(
+                path,
+                {
+                    "version": self.SCHEMA_VERSION,
+                    "checksum": _checksum(v1),
+                    "v1": v1,
+                },
+            )
         with self._lock:
             self._cache[claim.claim_uid] = claim
             self._absent.discard(claim.claim_uid)
@@ -149,7 +164,15 @@ class CheckpointStore:
     def _read_disk(self, claim_uid: str) -> Optional[PreparedClaim]:
         path = self._path(claim_uid)
         try:
-            obj = read_json(path)
+            nat = atomicfile.native()
+            if nat is not None:
+                # the miss before every fresh prepare: None, no exception
+                raw = nat.read_or_none(path)
+                if raw is None:
+                    return None
+                obj = json.loads(raw)
+            else:
+                obj = read_json(path)
         except FileNotFoundError:
             return None
         except (json.JSONDecodeError, OSError) as e:

@@ -6,7 +6,7 @@ from setuptools import Command, find_packages, setup
 
 
 class BuildNative(Command):
-    description = "build in-tree native extensions (_amdhal, _hiphealth)"
+    description = "build in-tree native extensions (_amdhal, _hiphealth, _claimio)"
     user_options = [("inplace", "i", "build into the package dir (always on)")]
 
     def initialize_options(self):
