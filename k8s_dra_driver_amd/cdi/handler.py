@@ -23,6 +23,7 @@ from .spec import (
     CDISpec,
     ContainerEdits,
     DeviceNode,
+    Mount,
     qualified_device_id,
     write_spec_file,
 )
@@ -124,8 +125,6 @@ class CDIHandler:
         if self.driver_version:
             common.env.append(f"AMD_DRIVER_VERSION={self.driver_version}")
         if self.rocm_mount:
-            from .spec import Mount
-
             common.mounts.append(
                 Mount(host_path=self.rocm_mount, container_path="/opt/rocm")
             )
@@ -170,6 +169,9 @@ class CDIHandler:
         # checkpoint (prepare's cache-hit path calls _ensure_claim_spec)
         write_spec_file(spec, path, durable=False)
         return path
+
+    def has_claim_spec(self, claim_uid: str) -> bool:
+        return os.path.exists(self._claim_spec_path(claim_uid))
 
     def delete_claim_spec(self, claim_uid: str) -> None:
         """Idempotent delete (cdi.go:281-284 analog)."""

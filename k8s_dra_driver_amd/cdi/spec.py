@@ -62,6 +62,11 @@ class Mount:
             "options": list(self.options),
         }
 
+    @classmethod
+    def from_json(cls, d: dict) -> "Mount":
+        """Inverse of ``to_json`` (a checkpointed claim mount)."""
+        return cls(d["hostPath"], d["containerPath"], list(d.get("options") or []))
+
 
 @dataclass
 class Hook:

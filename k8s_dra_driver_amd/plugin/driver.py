@@ -129,7 +129,7 @@ class Driver:
             node_uid=node_uid,
         )
         self.publisher.on_heal = self.metrics.slice_heals.inc
-        self.state.on_deferred_restores_change = (
+        self.state.ledger.on_deferred_restores_change = (
             self.metrics.deferred_restores.set
         )
         self._pool = ThreadPoolExecutor(
@@ -137,7 +137,7 @@ class Driver:
         )
         # Republish whenever the allocatable set changes (repartition).
         self.state.on_allocatable_change = self.publish_resources
-        self.state.on_repartition = self.metrics.repartitions.inc
+        self.state.ledger.on_repartition = self.metrics.repartitions.inc
         self.state.on_warning = self._emit_claim_warning
         # Failure detection: unhealthy GPUs are pulled from publication
         # (start()ed by main.py; tests drive check_once directly).

@@ -25,12 +25,11 @@ from __future__ import annotations
 
 import contextlib
 import logging
-import os
 import re
 import threading
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 from ..api.types import (
     ConfigError,
@@ -43,17 +42,15 @@ from ..api.types import (
     select_config_for_request,
 )
 from ..cdi.handler import CDIHandler
-from ..cdi.spec import ContainerEdits
+from ..cdi.spec import ContainerEdits, Mount
 from ..hal.base import DeviceLib
 from ..hal.model import AllocatableDevice
-from ..partition.manager import (
-    PartitionManager,
-    RepartitionFailed,
-    RepartitionRefused,
-)
-from ..sharing.shared import SharedComputeManager
+from ..partition.catalog import preferred_memory_mode
+from ..partition.manager import PartitionManager
+from ..sharing.shared import SharedComputeManager, SharedSession
 from ..sharing.timeslice import TimeSlicingManager
 from .checkpoint import CheckpointStore, PreparedClaim, PreparedDevice
+from .repartition import PrepareError, RepartitionLedger
 
 log = logging.getLogger(__name__)
 
@@ -61,10 +58,6 @@ DRIVER_NAME = "gpu.amd.com"
 
 #: canonical partition device name: gpu-<index>-<mode>-<pid>
 _PARTITION_NAME_RE = re.compile(r"^gpu-(\d+)-([a-z]+)-(\d+)$")
-
-
-class PrepareError(RuntimeError):
-    pass
 
 
 class _RefLock:
@@ -92,6 +85,11 @@ def _parse_claim_meta(claim: dict) -> _ClaimInfo:
     return _ClaimInfo(uid=uid, namespace=meta.get("namespace", ""), name=meta.get("name", ""))
 
 
+def _strategy(gcfg: Optional[GpuConfig]) -> str:
+    """The sharing strategy a request's GpuConfig asks for ("" = none)."""
+    return gcfg.sharing.strategy if gcfg and gcfg.sharing else ""
+
+
 class DeviceState:
     def __init__(
         self,
@@ -113,6 +111,8 @@ class DeviceState:
         self.partition_manager = partition_manager or PartitionManager(
             lib, in_use_fn=self.claims_holding_gpu
         )
+        #: holders, deferred restores, mode switches; the Driver sets on_* on it
+        self.ledger = RepartitionLedger(self.partition_manager, self._resync)
 
         #: optional callback fired after the allocatable set changes
         #: (repartition) — the Driver republishes ResourceSlices from it.
@@ -120,10 +120,6 @@ class DeviceState:
         #: optional callback(claim_info, reason, message) for user-facing
         #: Warning events (e.g. advisory time-slicing); wired by Driver
         self.on_warning = None
-        #: optional callback per performed mode switch (metrics)
-        self.on_repartition = None
-        #: optional callback(count) when the deferred-restore set changes
-        self.on_deferred_restores_change = None
 
         self._registry_lock = threading.Lock()
         self._claim_locks: Dict[str, "_RefLock"] = {}
@@ -131,11 +127,6 @@ class DeviceState:
         self._write_pool = ThreadPoolExecutor(
             max_workers=4, thread_name_prefix="cdi-write"
         )
-        #: gpu_index -> set of claim uids with prepared devices on it
-        self._gpu_holders: Dict[int, set] = {}
-        #: gpu_index -> (compute, memory) restore that was refused while
-        #: other claims held the GPU; retried when the GPU drains
-        self._deferred_restores: Dict[int, tuple] = {}
         #: canonical name -> AllocatableDevice
         self._allocatable: Dict[str, AllocatableDevice] = {}
         self.refresh_allocatable()
@@ -174,6 +165,11 @@ class DeviceState:
     def write_base_cdi_spec(self) -> str:
         return self.cdi.create_standard_spec(self.allocatable_devices())
 
+    def _resync(self) -> None:
+        """Bring publication back in line with hardware that (may have) moved."""
+        self.refresh_allocatable()
+        self.write_base_cdi_spec()
+
     # ------------------------------------------------------------------
     # recovery (crash-safe resume; reference device_state.go:94-125)
     # ------------------------------------------------------------------
@@ -211,35 +207,37 @@ class DeviceState:
                     uid,
                     missing,
                 )
-            for dev in pc.devices:
-                if dev.parent_gpu_index >= 0 and not dev.admin:
-                    self._gpu_holders.setdefault(dev.parent_gpu_index, set()).add(uid)
-            # Re-register shared sessions so CU-range bookkeeping survives
-            # a plugin restart (stale-state gap the reference leaves open,
-            # SURVEY.md §5.4).
-            if pc.sharing_strategy == SHARED_COMPUTE and self.shared_manager:
-                from ..sharing.shared import SharedSession
-
-                spec_uids = set(self.cdi.list_claim_spec_uids())
-                if uid in spec_uids:
-                    # claim_env carries the checkpointed HSA_CU_MASK entries;
-                    # recover_session parses them back into CU-range
-                    # bookkeeping so a post-restart SharedCompute claim on the
-                    # same GPU cannot be handed an overlapping CU slice.
-                    self.shared_manager.recover_session(
-                        SharedSession(
-                            session_id=pc.shared_session_id or uid[:36],
-                            claim_uid=uid,
-                            shm_dir="",
-                            env=list(pc.claim_env),
-                            mounts=[],
-                            gpu_indices=[
-                                d.parent_gpu_index for d in pc.devices
-                            ],
-                        )
-                    )
+            self.ledger.hold(uid, pc.devices)
+        self._recover_shared_sessions(recovered.values())
         if recovered:
             log.info("recovered %d prepared claim(s) from checkpoints", len(recovered))
+
+    def _recover_shared_sessions(self, claims) -> None:
+        """Re-register shared sessions so CU-range bookkeeping survives a
+        plugin restart (stale-state gap the reference leaves open,
+        SURVEY.md §5.4)."""
+        shared_claims = [pc for pc in claims if pc.sharing_strategy == SHARED_COMPUTE]
+        if not (shared_claims and self.shared_manager):
+            return
+        # listed once, and only after _recover has regenerated every
+        # missing claim spec
+        spec_uids = set(self.cdi.list_claim_spec_uids())
+        for pc in shared_claims:
+            if pc.claim_uid in spec_uids:
+                # claim_env carries the checkpointed HSA_CU_MASK entries;
+                # recover_session parses them back into CU-range
+                # bookkeeping so a post-restart SharedCompute claim on the
+                # same GPU cannot be handed an overlapping CU slice.
+                self.shared_manager.recover_session(
+                    SharedSession(
+                        session_id=pc.shared_session_id or pc.claim_uid[:36],
+                        claim_uid=pc.claim_uid,
+                        shm_dir="",
+                        env=list(pc.claim_env),
+                        mounts=[],
+                        gpu_indices=[d.parent_gpu_index for d in pc.devices],
+                    )
+                )
 
     # ------------------------------------------------------------------
     # locking
@@ -266,8 +264,7 @@ class DeviceState:
                     del self._claim_locks[uid]
 
     def claims_holding_gpu(self, gpu_index: int) -> List[str]:
-        with self._registry_lock:
-            return sorted(self._gpu_holders.get(gpu_index, set()))
+        return self.ledger.holders(gpu_index)
 
     # ------------------------------------------------------------------
     # prepare
@@ -283,23 +280,14 @@ class DeviceState:
                 return [self._to_kubelet_device(d) for d in cached.devices]
 
             results, configs = self._parse_allocation(claim)
-            prepared = self._prepare_devices(info, results, configs)
+            prepared, spec_write = self._prepare_devices(info, results, configs)
             try:
                 self.checkpoints.write(prepared)
-                fut = getattr(prepared, "_cdi_write", None)
-                if fut is not None:
-                    fut.result()  # join the overlapped claim-spec write
+                spec_write.result()  # join the overlapped claim-spec write
             except BaseException:
                 self._rollback(prepared, info.uid)
                 raise
-            with self._registry_lock:
-                for dev in prepared.devices:
-                    # adminAccess (monitoring) claims neither block
-                    # repartition drains nor count as exclusive holders
-                    if dev.parent_gpu_index >= 0 and not dev.admin:
-                        self._gpu_holders.setdefault(
-                            dev.parent_gpu_index, set()
-                        ).add(info.uid)
+            self.ledger.hold(info.uid, prepared.devices)
             return [self._to_kubelet_device(d) for d in prepared.devices]
 
     def _parse_allocation(self, claim: dict):
@@ -338,11 +326,9 @@ class DeviceState:
         return results, configs
 
     def _prepare_devices(
-        self,
-        info: _ClaimInfo,
-        results: List[dict],
-        configs: List[OpaqueConfig],
-    ) -> PreparedClaim:
+        self, info: _ClaimInfo, results: List[dict], configs: List[OpaqueConfig]
+    ) -> Tuple[PreparedClaim, Future]:
+        """Returns the prepared claim and its in-flight claim-spec write."""
         prepared = PreparedClaim(
             claim_uid=info.uid, namespace=info.namespace, name=info.name
         )
@@ -360,35 +346,13 @@ class DeviceState:
                 dev = self._find_device(r["device"])
                 if dev is None or dev.kind != "gpu":
                     continue
-                gpu_index = dev.parent_gpu.index
-                try:
-                    cur = dev.parent_gpu
-                    switched = self.partition_manager.ensure_mode(
-                        gpu_index,
-                        pcfg.compute_partition,
-                        pcfg.memory_partition,
-                        requesting_claim=info.uid,
-                        allow_dynamic=pcfg.allow_dynamic_repartition,
-                    )
-                except RepartitionRefused as e:
-                    raise PrepareError(str(e)) from e
-                except RepartitionFailed as e:
-                    self._note_failed_switch(gpu_index, e)
-                    raise PrepareError(str(e)) from e
-                except Exception as e:
-                    # HAL failure mid-switch: surface typed, and let the
-                    # outer rollback undo any PRIOR switch of this claim
-                    raise PrepareError(
-                        f"repartition of gpu-{gpu_index} failed: {e}"
-                    ) from e
-                if switched:
-                    if self.on_repartition is not None:
-                        self.on_repartition()
-                    prepared.repartitioned[str(gpu_index)] = [
-                        cur.compute_partition,
-                        cur.memory_partition,
-                        pcfg.compute_partition,
-                        pcfg.memory_partition,
+                cur = dev.parent_gpu
+                target = [pcfg.compute_partition, pcfg.memory_partition]
+                if self.ledger.switch_for_claim(
+                    cur.index, *target, info.uid, allow_dynamic=pcfg.allow_dynamic_repartition
+                ):
+                    prepared.repartitioned[str(cur.index)] = [
+                        cur.compute_partition, cur.memory_partition, *target
                     ]
                     repartition_done = True
             # Scheduler-driven carve (DRA partitionable devices): an
@@ -407,11 +371,10 @@ class DeviceState:
                 self._rollback(prepared, info.uid)
             raise
         if repartition_done:
-            self.refresh_allocatable()
-            self.write_base_cdi_spec()
+            self._resync()
 
         try:
-            return self._prepare_after_partition(info, results, configs, prepared)
+            return prepared, self._prepare_after_partition(info, results, configs, prepared)
         except BaseException:
             # a failure past a successful mode switch must not leak it
             self._rollback(prepared, info.uid)
@@ -420,8 +383,6 @@ class DeviceState:
     def _auto_carve_for_results(
         self, info: _ClaimInfo, results: List[dict], prepared: PreparedClaim
     ) -> bool:
-        from ..partition.catalog import preferred_memory_mode
-
         changed = False
         for r in results:
             name = r.get("device", "")
@@ -439,39 +400,11 @@ class DeviceState:
             if gpu is None or gpu.compute_partition == mode:
                 continue  # unknown GPU, or carved but pid out of range
             mem = preferred_memory_mode(mode, gpu.nps_caps)
-            try:
-                switched = self.partition_manager.ensure_mode(
-                    gpu_index,
-                    mode,
-                    mem,
-                    requesting_claim=info.uid,
-                    allow_dynamic=True,
-                )
-            except RepartitionRefused as e:
-                raise PrepareError(
-                    f"allocated device {name!r} requires carving "
-                    f"gpu-{gpu_index} to {mode}: {e}"
-                ) from e
-            except RepartitionFailed as e:
-                self._note_failed_switch(gpu_index, e)
-                raise PrepareError(
-                    f"auto-carve of gpu-{gpu_index} to {mode} failed: {e}"
-                ) from e
-            except Exception as e:
-                raise PrepareError(
-                    f"auto-carve of gpu-{gpu_index} to {mode} failed: {e}"
-                ) from e
-            if switched:
-                if self.on_repartition is not None:
-                    self.on_repartition()
+            if self.ledger.switch_for_claim(
+                gpu_index, mode, mem, info.uid, allow_dynamic=True, carve_for=name
+            ):
                 prepared.repartitioned.setdefault(
-                    str(gpu_index),
-                    [
-                        gpu.compute_partition,
-                        gpu.memory_partition,
-                        mode,
-                        mem,
-                    ],
+                    str(gpu_index), [gpu.compute_partition, gpu.memory_partition, mode, mem]
                 )
                 log.info(
                     "claim %s: auto-carved gpu-%d to %s/%s for "
@@ -491,8 +424,41 @@ class DeviceState:
         results: List[dict],
         configs: List[OpaqueConfig],
         prepared: PreparedClaim,
-    ) -> PreparedClaim:
-        # --- group results by sharing config -------------------------------
+    ) -> Future:
+        """Sharing, claim spec and response for the resolved devices; fills
+        ``prepared`` and returns the in-flight claim-spec write."""
+        per_result_dev = self._resolve_devices(results)
+        gcfg_by_dev = [
+            (select_config_for_request(r.get("request", ""), configs, GpuConfig), dev)
+            for r, dev in per_result_dev
+        ]
+        shared_edits = self._start_shared_compute(info, gcfg_by_dev, prepared)
+        self._apply_time_slices(info, gcfg_by_dev, prepared)
+
+        claim_edits = ContainerEdits(
+            env=[f"AMD_DRA_CLAIM_UID={info.uid}"]
+        )
+        if shared_edits is not None:
+            claim_edits = claim_edits.merge(shared_edits)
+        prepared.claim_env = list(claim_edits.env)
+        prepared.claim_mounts = [m.to_json() for m in claim_edits.mounts]
+        device_names = [dev.canonical_name for _, dev in per_result_dev]
+        # Overlap the claim-spec write with building the response and the
+        # checkpoint written by the caller: the spec is regenerable from
+        # the checkpoint (see prepare()'s cache-hit path), so ordering is
+        # no longer a crash-safety requirement. prepare() joins the
+        # returned future. The spec is no longer fsynced, but its native
+        # write runs with the GIL released and still overlaps: on an
+        # MI355X node the handoff measured 3-5% more pods/s than the same
+        # call made inline (profiles/claimio_r03.md).
+        spec_write = self._write_pool.submit(
+            self.cdi.create_claim_spec, info.uid, device_names, claim_edits
+        )
+        self._build_response(info, per_result_dev, prepared)
+        return spec_write
+
+    def _resolve_devices(self, results: List[dict]) -> List[tuple]:
+        """(result, AllocatableDevice) pairs for every allocation result."""
         per_result_dev: List[tuple] = []
         for r in results:
             name = r.get("device", "")
@@ -506,44 +472,33 @@ class DeviceState:
                         f"allocated device {name!r} not found on this node "
                         f"(ResourceSlice drift? plugin will republish)"
                     )
-                for p in parts:
-                    per_result_dev.append((r, p))
+                per_result_dev.extend((r, p) for p in parts)
             else:
                 per_result_dev.append((r, dev))
+        return per_result_dev
 
-        # --- sharing --------------------------------------------------------
-        shared_edits: Optional[ContainerEdits] = None
-        gcfg_by_dev: List[tuple] = []
-        strategies = set()
-        for r, dev in per_result_dev:
-            gcfg = select_config_for_request(r.get("request", ""), configs, GpuConfig)
-            gcfg_by_dev.append((gcfg, dev))
-            if gcfg and gcfg.sharing:
-                strategies.add(gcfg.sharing.strategy)
-
-        if SHARED_COMPUTE in strategies:
-            if self.shared_manager is None:
-                raise PrepareError("SharedCompute requested but supervisor disabled")
-            sc_devices = [
-                dev
-                for gcfg, dev in gcfg_by_dev
-                if gcfg and gcfg.sharing and gcfg.sharing.strategy == SHARED_COMPUTE
-            ]
-            settings = next(
-                gcfg.sharing.shared_compute
-                for gcfg, _ in gcfg_by_dev
-                if gcfg and gcfg.sharing and gcfg.sharing.strategy == SHARED_COMPUTE
+    def _start_shared_compute(
+        self, info: _ClaimInfo, gcfg_by_dev: List[tuple], prepared: PreparedClaim
+    ) -> Optional[ContainerEdits]:
+        """One session over the claim's SharedCompute devices -> its edits."""
+        shared = [(g, dev) for g, dev in gcfg_by_dev if _strategy(g) == SHARED_COMPUTE]
+        if not shared:
+            return None
+        if self.shared_manager is None:
+            raise PrepareError("SharedCompute requested but supervisor disabled")
+        try:
+            session = self.shared_manager.start_session(
+                info.uid, [dev for _, dev in shared], shared[0][0].sharing.shared_compute
             )
-            try:
-                session = self.shared_manager.start_session(
-                    info.uid, sc_devices, settings
-                )
-            except Exception as e:
-                raise PrepareError(f"shared-compute session failed: {e}") from e
-            prepared.sharing_strategy = SHARED_COMPUTE
-            prepared.shared_session_id = session.session_id
-            shared_edits = session.container_edits()
+        except Exception as e:
+            raise PrepareError(f"shared-compute session failed: {e}") from e
+        prepared.sharing_strategy = SHARED_COMPUTE
+        prepared.shared_session_id = session.session_id
+        return session.container_edits()
 
+    def _apply_time_slices(
+        self, info: _ClaimInfo, gcfg_by_dev: List[tuple], prepared: PreparedClaim
+    ) -> None:
         # Group time-sliced devices by their settings: two requests in one
         # claim may carry different intervals, and collapsing them to the
         # first match would silently mis-apply (round-1 "weak" finding).
@@ -552,14 +507,11 @@ class DeviceState:
         ts_by_quantum: Dict[int, tuple] = {}
         gpu_interval: Dict[int, str] = {}
         for gcfg, dev in gcfg_by_dev:
-            if not (
-                gcfg
-                and gcfg.sharing
-                and gcfg.sharing.strategy == TIME_SLICING
-                and gcfg.sharing.time_slicing.interval != "Default"
-            ):
+            if _strategy(gcfg) != TIME_SLICING:
                 continue
             ts = gcfg.sharing.time_slicing
+            if ts.interval == "Default":
+                continue
             idx = dev.parent_gpu.index
             if gpu_interval.get(idx, ts.interval) != ts.interval:
                 raise PrepareError(
@@ -569,59 +521,40 @@ class DeviceState:
             gpu_interval[idx] = ts.interval
             entry = ts_by_quantum.setdefault(ts.quantum_us, (ts, []))
             entry[1].append(dev)
-        if ts_by_quantum:
-            for settings, devs in ts_by_quantum.values():
-                try:
-                    prepared.timeslice_gpus.extend(
-                        self.ts_manager.set_timeslice(devs, settings)
-                    )
-                except Exception as e:
-                    # _rollback (invoked by the caller) undoes the session
-                    raise PrepareError(f"time-slicing failed: {e}") from e
-            if not prepared.sharing_strategy:
-                prepared.sharing_strategy = TIME_SLICING
-            if not self.lib.timeslice_effective():
-                # Surface the platform gap instead of silently reporting
-                # success: this hardware has no runtime
-                # scheduler-quantum control, so the interval is advisory.
-                msg = (
-                    "TimeSlicing interval(s) "
-                    f"{sorted(set(gpu_interval.values()))} accepted but "
-                    "ADVISORY on this node: amdgpu exposes no runtime "
-                    "scheduler-quantum control (timeSlicingEffective=false "
-                    "on the published devices); HSA default queue "
-                    "multiplexing applies"
+        if not ts_by_quantum:
+            return
+        for settings, devs in ts_by_quantum.values():
+            try:
+                prepared.timeslice_gpus.extend(
+                    self.ts_manager.set_timeslice(devs, settings)
                 )
-                log.warning("claim %s: %s", info.uid, msg)
-                if self.on_warning is not None:
-                    try:
-                        self.on_warning(info, "TimeSlicingAdvisory", msg)
-                    except Exception:
-                        log.exception("warning callback failed")
+            except Exception as e:
+                # _rollback (invoked by the caller) undoes the session
+                raise PrepareError(f"time-slicing failed: {e}") from e
+        if not prepared.sharing_strategy:
+            prepared.sharing_strategy = TIME_SLICING
+        if not self.lib.timeslice_effective():
+            # Surface the platform gap instead of silently reporting
+            # success: this hardware has no runtime
+            # scheduler-quantum control, so the interval is advisory.
+            msg = (
+                "TimeSlicing interval(s) "
+                f"{sorted(set(gpu_interval.values()))} accepted but "
+                "ADVISORY on this node: amdgpu exposes no runtime "
+                "scheduler-quantum control (timeSlicingEffective=false "
+                "on the published devices); HSA default queue "
+                "multiplexing applies"
+            )
+            log.warning("claim %s: %s", info.uid, msg)
+            if self.on_warning is not None:
+                try:
+                    self.on_warning(info, "TimeSlicingAdvisory", msg)
+                except Exception:
+                    log.exception("warning callback failed")
 
-        # --- CDI claim spec -------------------------------------------------
-        claim_edits = ContainerEdits(
-            env=[f"AMD_DRA_CLAIM_UID={info.uid}"]
-        )
-        if shared_edits is not None:
-            claim_edits = claim_edits.merge(shared_edits)
-        prepared.claim_env = list(claim_edits.env)
-        prepared.claim_mounts = [m.to_json() for m in claim_edits.mounts]
-        device_names = [dev.canonical_name for _, dev in per_result_dev]
-        # Overlap the claim-spec write with building the response and the
-        # checkpoint written by the caller: the spec is regenerable from
-        # the checkpoint (see prepare()'s cache-hit path), so ordering is
-        # no longer a crash-safety requirement. The future rides on the
-        # (per-claim) prepared object; prepare() joins it. The spec is no
-        # longer fsynced, but its native write runs with the GIL released
-        # and still overlaps: on an MI355X node the handoff measured 3-5%
-        # more pods/s than the same call made inline
-        # (profiles/claimio_r03.md).
-        prepared._cdi_write = self._write_pool.submit(
-            self.cdi.create_claim_spec, info.uid, device_names, claim_edits
-        )
-
-        # --- response -------------------------------------------------------
+    def _build_response(
+        self, info: _ClaimInfo, per_result_dev: List[tuple], prepared: PreparedClaim
+    ) -> None:
         for r, dev in per_result_dev:
             prepared.devices.append(
                 PreparedDevice(
@@ -638,7 +571,6 @@ class DeviceState:
                     admin=bool(r.get("adminAccess")),
                 )
             )
-        return prepared
 
     def _rollback(self, prepared: PreparedClaim, claim_uid: str) -> None:
         """Best-effort undo of a partially-prepared claim: stop the shared
@@ -650,40 +582,7 @@ class DeviceState:
                 self.shared_manager.stop_session(prepared.shared_session_id)
             if prepared.timeslice_gpus:
                 self.ts_manager.restore_default(prepared.timeslice_gpus)
-            reverted = False
-            for gpu_index_s, modes in prepared.repartitioned.items():
-                try:
-                    if self.partition_manager.ensure_mode(
-                        int(gpu_index_s),
-                        modes[0],
-                        modes[1],
-                        requesting_claim=claim_uid,
-                        allow_dynamic=True,
-                    ):
-                        reverted = True
-                except RepartitionRefused as e:
-                    log.warning(
-                        "rollback: leaving gpu-%s partitioned (%s)",
-                        gpu_index_s,
-                        e,
-                    )
-                except Exception as e:
-                    # revert itself failed (transient HAL error): remember
-                    # the target mode and retry when the GPU drains
-                    self._deferred_restores.setdefault(
-                        int(gpu_index_s), (modes[0], modes[1])
-                    )
-                    self._notify_deferred()
-                    reverted = True  # hardware may have moved: re-sync
-                    log.warning(
-                        "rollback: revert of gpu-%s failed (%s); restore "
-                        "deferred",
-                        gpu_index_s,
-                        e,
-                    )
-            if reverted:
-                self.refresh_allocatable()
-                self.write_base_cdi_spec()
+            self.ledger.revert(prepared.repartitioned, claim_uid)
             self.cdi.delete_claim_spec(claim_uid)
             self.checkpoints.delete(claim_uid)
         except Exception:
@@ -692,25 +591,12 @@ class DeviceState:
     def _ensure_claim_spec(self, pc: PreparedClaim) -> None:
         """Regenerate the claim CDI spec if a crash between the overlapped
         writes (or manual deletion) left it missing."""
-        path = self.cdi._claim_spec_path(pc.claim_uid)
-        if os.path.exists(path):
+        if self.cdi.has_claim_spec(pc.claim_uid):
             return
-        from ..cdi.spec import Mount
-
         edits = ContainerEdits(
-            env=list(pc.claim_env),
-            mounts=[
-                Mount(
-                    host_path=m["hostPath"],
-                    container_path=m["containerPath"],
-                    options=list(m.get("options") or []),
-                )
-                for m in pc.claim_mounts
-            ],
+            env=list(pc.claim_env), mounts=[Mount.from_json(m) for m in pc.claim_mounts]
         )
-        self.cdi.create_claim_spec(
-            pc.claim_uid, [d.device_name for d in pc.devices], edits
-        )
+        self.cdi.create_claim_spec(pc.claim_uid, [d.device_name for d in pc.devices], edits)
 
     def _find_device(self, name: str) -> Optional[AllocatableDevice]:
         with self._registry_lock:
@@ -745,11 +631,8 @@ class DeviceState:
                 # unknown claim: no-op (:171-173) — but still sweep any
                 # deferred mode restores (a concurrent batch drain can
                 # leave one pending with no further real unprepare)
-                if self._deferred_restores and self._retry_deferred_restores(
-                    claim_uid
-                ):
-                    self.refresh_allocatable()
-                    self.write_base_cdi_spec()
+                if self.ledger.retry_deferred(claim_uid):
+                    self._resync()
                 return
 
             if pc.sharing_strategy == SHARED_COMPUTE and self.shared_manager:
@@ -757,96 +640,8 @@ class DeviceState:
             if pc.timeslice_gpus:
                 self.ts_manager.restore_default(pc.timeslice_gpus)
 
-            # Release holdership BEFORE attempting mode restore so our own
-            # claim does not block the drain check.
-            with self._registry_lock:
-                for holders in self._gpu_holders.values():
-                    holders.discard(claim_uid)
-
-            restored = False
-            for gpu_index_s, modes in pc.repartitioned.items():
-                prev_c, prev_m = modes[0], modes[1]
-                try:
-                    if self.partition_manager.ensure_mode(
-                        int(gpu_index_s),
-                        prev_c,
-                        prev_m,
-                        requesting_claim=claim_uid,
-                        allow_dynamic=True,
-                    ):
-                        restored = True
-                        if self.on_repartition is not None:
-                            self.on_repartition()
-                except RepartitionRefused as e:
-                    # other claims still hold partitions of this GPU;
-                    # remember the restore and retry when it drains
-                    self._deferred_restores[int(gpu_index_s)] = (
-                        prev_c,
-                        prev_m,
-                    )
-                    self._notify_deferred()
-                    log.warning(
-                        "leaving gpu-%s partitioned for now (%s); restore "
-                        "deferred until the GPU drains",
-                        gpu_index_s,
-                        e,
-                    )
-            if self._retry_deferred_restores(claim_uid):
-                restored = True
-            if restored:
-                self.refresh_allocatable()
-                self.write_base_cdi_spec()
+            # releases holdership BEFORE it restores modes and retries
+            self.ledger.release(claim_uid, pc.repartitioned)
 
             self.cdi.delete_claim_spec(claim_uid)
             self.checkpoints.delete(claim_uid)
-
-    def _note_failed_switch(self, gpu_index: int, e: RepartitionFailed) -> None:
-        """A mode switch died mid-sequence. If the manager's revert did
-        not restore the original mode, remember it as a deferred restore
-        (retried on every unprepare) and re-sync publication with the
-        actual hardware state."""
-        if not e.reverted:
-            self._deferred_restores.setdefault(gpu_index, e.original)
-            self._notify_deferred()
-            self.refresh_allocatable()
-            self.write_base_cdi_spec()
-
-    def _notify_deferred(self) -> None:
-        if self.on_deferred_restores_change is not None:
-            try:
-                self.on_deferred_restores_change(len(self._deferred_restores))
-            except Exception:
-                pass
-
-    def _retry_deferred_restores(self, requesting_claim: str) -> bool:
-        """Apply deferred mode restores for GPUs that have drained (the
-        last pod of a scheduler-carved GPU left: return it to SPX so the
-        whole-GPU device becomes allocatable again)."""
-        restored = False
-        for gpu_index in list(self._deferred_restores):
-            if self.claims_holding_gpu(gpu_index):
-                continue
-            prev_c, prev_m = self._deferred_restores[gpu_index]
-            try:
-                if self.partition_manager.ensure_mode(
-                    gpu_index,
-                    prev_c,
-                    prev_m,
-                    requesting_claim=requesting_claim,
-                    allow_dynamic=True,
-                ):
-                    restored = True
-                    if self.on_repartition is not None:
-                        self.on_repartition()
-                    log.info(
-                        "gpu-%d drained: deferred restore to %s/%s applied",
-                        gpu_index,
-                        prev_c,
-                        prev_m,
-                    )
-                del self._deferred_restores[gpu_index]
-                self._notify_deferred()
-            except Exception:
-                pass  # raced a new prepare or transient HAL failure:
-                      # keep the entry, retried on the next unprepare
-        return restored

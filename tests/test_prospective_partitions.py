@@ -286,5 +286,5 @@ def test_concurrent_batch_drain_eventually_restores(driver):
     if lib.enumerate()[5].compute_partition != "SPX":
         # race window: retry fires on the next unprepare of anything
         d.state.unprepare("no-such-claim")
-        d.state._retry_deferred_restores("sweep")
+        d.state.ledger.retry_deferred("sweep")
     assert lib.enumerate()[5].compute_partition == "SPX"
