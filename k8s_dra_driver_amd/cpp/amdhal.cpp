@@ -11,6 +11,7 @@
 //   enumerate()                -> list[dict] per physical GPU
 //   set_compute_partition(i, "SPX|DPX|TPX|QPX|CPX")
 //   set_memory_partition(i, "NPS1|NPS2|NPS4|NPS8")
+//   health_signals(i)          -> dict of RAS / thermal telemetry (read-only)
 //
 // Build: hipcc/amdclang++ -shared -fPIC $(python -m pybind11 --includes)
 //        amdhal.cpp -lamd_smi -o _amdhal.so   (driven by setup.py)
@@ -250,6 +251,238 @@ void hal_set_memory_partition(size_t index, const std::string& mode) {
                                         memory_mode_from_string(mode)));
 }
 
+// ---------------------------------------------------------------------------
+// Passive health signals: RAS counters, retired pages, temperatures and
+// throttle flags the amdgpu driver already keeps. Read-only; nothing is
+// launched on the device.
+// ---------------------------------------------------------------------------
+
+std::string status_string(amdsmi_status_t st) {
+  const char* msg = nullptr;
+  amdsmi_status_code_to_string(st, &msg);
+  return msg ? std::string(msg) : ("status " + std::to_string(st));
+}
+
+struct BlockName {
+  amdsmi_gpu_block_t block;
+  const char* name;
+};
+
+const BlockName kEccBlocks[] = {
+    {AMDSMI_GPU_BLOCK_UMC, "UMC"},
+    {AMDSMI_GPU_BLOCK_SDMA, "SDMA"},
+    {AMDSMI_GPU_BLOCK_GFX, "GFX"},
+    {AMDSMI_GPU_BLOCK_MMHUB, "MMHUB"},
+    {AMDSMI_GPU_BLOCK_ATHUB, "ATHUB"},
+    {AMDSMI_GPU_BLOCK_PCIE_BIF, "PCIE_BIF"},
+    {AMDSMI_GPU_BLOCK_HDP, "HDP"},
+    {AMDSMI_GPU_BLOCK_XGMI_WAFL, "XGMI_WAFL"},
+    {AMDSMI_GPU_BLOCK_DF, "DF"},
+    {AMDSMI_GPU_BLOCK_SMN, "SMN"},
+    {AMDSMI_GPU_BLOCK_SEM, "SEM"},
+    {AMDSMI_GPU_BLOCK_MP0, "MP0"},
+    {AMDSMI_GPU_BLOCK_MP1, "MP1"},
+    {AMDSMI_GPU_BLOCK_FUSE, "FUSE"},
+    {AMDSMI_GPU_BLOCK_MCA, "MCA"},
+    {AMDSMI_GPU_BLOCK_VCN, "VCN"},
+    {AMDSMI_GPU_BLOCK_JPEG, "JPEG"},
+    {AMDSMI_GPU_BLOCK_IH, "IH"},
+    {AMDSMI_GPU_BLOCK_MPIO, "MPIO"},
+};
+
+struct TempRead {
+  const char* name;
+  amdsmi_temperature_type_t sensor;
+  amdsmi_temperature_metric_t metric;
+};
+
+const TempRead kTemps[] = {
+    {"temp_hotspot_c", AMDSMI_TEMPERATURE_TYPE_HOTSPOT, AMDSMI_TEMP_CURRENT},
+    {"temp_hotspot_crit_c", AMDSMI_TEMPERATURE_TYPE_HOTSPOT,
+     AMDSMI_TEMP_CRITICAL},
+    {"temp_vram_c", AMDSMI_TEMPERATURE_TYPE_VRAM, AMDSMI_TEMP_CURRENT},
+    {"temp_vram_crit_c", AMDSMI_TEMPERATURE_TYPE_VRAM, AMDSMI_TEMP_CRITICAL},
+};
+constexpr size_t kNumTemps = sizeof(kTemps) / sizeof(kTemps[0]);
+
+const char* const kThrottleNames[] = {
+    "throttle_prochot",    "throttle_ppt",         "throttle_socket_thermal",
+    "throttle_vr_thermal", "throttle_hbm_thermal",
+};
+constexpr size_t kNumThrottles =
+    sizeof(kThrottleNames) / sizeof(kThrottleNames[0]);
+
+// Everything health_signals() reads, as plain data: filled with g_mutex
+// held and the GIL released, turned into Python objects only afterwards.
+struct RawHealth {
+  amdsmi_status_t total_st = AMDSMI_STATUS_SUCCESS;
+  amdsmi_error_count_t total{};
+
+  amdsmi_status_t enabled_st = AMDSMI_STATUS_SUCCESS;
+  struct Block {
+    const char* name;
+    amdsmi_status_t st;
+    amdsmi_error_count_t ec;
+  };
+  std::vector<Block> blocks;
+
+  amdsmi_status_t pages_st = AMDSMI_STATUS_SUCCESS;
+  uint64_t reserved = 0, pending = 0, unreservable = 0;
+
+  amdsmi_status_t threshold_st = AMDSMI_STATUS_SUCCESS;
+  uint32_t threshold = 0;
+
+  amdsmi_status_t temp_st[kNumTemps] = {};
+  int64_t temp[kNumTemps] = {};
+
+  amdsmi_status_t viol_st = AMDSMI_STATUS_SUCCESS;
+  uint8_t throttle[kNumThrottles] = {};
+};
+
+void read_health(amdsmi_processor_handle h, RawHealth& r) {
+  r.total_st = amdsmi_get_gpu_total_ecc_count(h, &r.total);
+
+  uint64_t enabled = 0;
+  r.enabled_st = amdsmi_get_gpu_ecc_enabled(h, &enabled);
+  if (r.enabled_st == AMDSMI_STATUS_SUCCESS) {
+    for (const auto& b : kEccBlocks) {
+      if (!(enabled & static_cast<uint64_t>(b.block))) continue;
+      RawHealth::Block blk{b.name, AMDSMI_STATUS_SUCCESS, {}};
+      blk.st = amdsmi_get_gpu_ecc_count(h, b.block, &blk.ec);
+      r.blocks.push_back(blk);
+    }
+  }
+
+  // Two calls: the first reports how many records there are, the second
+  // fills a buffer of that size.
+  uint32_t num_pages = 0;
+  r.pages_st = amdsmi_get_gpu_bad_page_info(h, &num_pages, nullptr);
+  if (r.pages_st == AMDSMI_STATUS_SUCCESS && num_pages > 0) {
+    std::vector<amdsmi_retired_page_record_t> pages(num_pages);
+    uint32_t filled = num_pages;
+    r.pages_st = amdsmi_get_gpu_bad_page_info(h, &filled, pages.data());
+    if (r.pages_st == AMDSMI_STATUS_SUCCESS) {
+      if (filled > num_pages) filled = num_pages;
+      for (uint32_t i = 0; i < filled; ++i) {
+        switch (pages[i].status) {
+          case AMDSMI_MEM_PAGE_STATUS_RESERVED:
+            ++r.reserved;
+            break;
+          case AMDSMI_MEM_PAGE_STATUS_PENDING:
+            ++r.pending;
+            break;
+          case AMDSMI_MEM_PAGE_STATUS_UNRESERVABLE:
+            ++r.unreservable;
+            break;
+        }
+      }
+    }
+  }
+
+  r.threshold_st = amdsmi_get_gpu_bad_page_threshold(h, &r.threshold);
+
+  for (size_t i = 0; i < kNumTemps; ++i)
+    r.temp_st[i] =
+        amdsmi_get_temp_metric(h, kTemps[i].sensor, kTemps[i].metric, &r.temp[i]);
+
+  amdsmi_violation_status_t v{};
+  r.viol_st = amdsmi_get_violation_status(h, &v);
+  if (r.viol_st == AMDSMI_STATUS_SUCCESS) {
+    r.throttle[0] = v.active_prochot_thrm;
+    r.throttle[1] = v.active_ppt_pwr;
+    r.throttle[2] = v.active_socket_thrm;
+    r.throttle[3] = v.active_vr_thrm;
+    r.throttle[4] = v.active_hbm_thrm;
+  }
+}
+
+py::dict error_count_dict(const amdsmi_error_count_t& ec) {
+  py::dict d;
+  d["correctable"] = ec.correctable_count;
+  d["uncorrectable"] = ec.uncorrectable_count;
+  d["deferred"] = ec.deferred_count;
+  return d;
+}
+
+// Every signal is reported exactly once: as a value, or under
+// "unsupported" with the AMD SMI status string. A refused call never
+// raises and never turns into a zero.
+py::dict hal_health_signals(size_t index) {
+  RawHealth raw;
+  {
+    // Lock order: the other entry points wait for g_mutex while holding
+    // the GIL, so the GIL must not be wanted while g_mutex is held. It is
+    // released first and taken back only after g_mutex is dropped (the
+    // guard below is destroyed before `nogil`).
+    py::gil_scoped_release nogil;
+    std::lock_guard<std::mutex> lock(g_mutex);
+    read_health(processor_at(index), raw);
+  }
+
+  py::dict out;
+  py::dict unsupported;
+
+  if (raw.total_st == AMDSMI_STATUS_SUCCESS) {
+    out["ecc_correctable"] = raw.total.correctable_count;
+    out["ecc_uncorrectable"] = raw.total.uncorrectable_count;
+    out["ecc_deferred"] = raw.total.deferred_count;
+  } else {
+    const std::string why = status_string(raw.total_st);
+    unsupported["ecc_correctable"] = why;
+    unsupported["ecc_uncorrectable"] = why;
+    unsupported["ecc_deferred"] = why;
+  }
+
+  if (raw.enabled_st == AMDSMI_STATUS_SUCCESS) {
+    py::dict blocks;
+    for (const auto& b : raw.blocks) {
+      if (b.st == AMDSMI_STATUS_SUCCESS)
+        blocks[b.name] = error_count_dict(b.ec);
+      else
+        unsupported[py::str(std::string("ecc_blocks.") + b.name)] =
+            status_string(b.st);
+    }
+    out["ecc_blocks"] = blocks;
+  } else {
+    unsupported["ecc_blocks"] = status_string(raw.enabled_st);
+  }
+
+  if (raw.pages_st == AMDSMI_STATUS_SUCCESS) {
+    out["bad_pages_reserved"] = raw.reserved;
+    out["bad_pages_pending"] = raw.pending;
+    out["bad_pages_unreservable"] = raw.unreservable;
+  } else {
+    const std::string why = status_string(raw.pages_st);
+    unsupported["bad_pages_reserved"] = why;
+    unsupported["bad_pages_pending"] = why;
+    unsupported["bad_pages_unreservable"] = why;
+  }
+
+  if (raw.threshold_st == AMDSMI_STATUS_SUCCESS)
+    out["bad_page_threshold"] = raw.threshold;
+  else
+    unsupported["bad_page_threshold"] = status_string(raw.threshold_st);
+
+  for (size_t i = 0; i < kNumTemps; ++i) {
+    if (raw.temp_st[i] == AMDSMI_STATUS_SUCCESS)
+      out[kTemps[i].name] = raw.temp[i];
+    else
+      unsupported[kTemps[i].name] = status_string(raw.temp_st[i]);
+  }
+
+  for (size_t i = 0; i < kNumThrottles; ++i) {
+    if (raw.viol_st != AMDSMI_STATUS_SUCCESS)
+      unsupported[kThrottleNames[i]] = status_string(raw.viol_st);
+    else if (raw.throttle[i] == 0xFF)
+      unsupported[kThrottleNames[i]] = "not reported (0xFF)";
+    else
+      out[kThrottleNames[i]] = raw.throttle[i] != 0;
+  }
+
+  out["unsupported"] = unsupported;
+  return out;
+}
+
 py::dict hal_lib_version() {
   py::dict out;
   amdsmi_version_t v{};
@@ -281,5 +514,8 @@ PYBIND11_MODULE(PYBIND11_MODULE_NAME, m) {
         py::arg("index"), py::arg("mode"));
   m.def("set_memory_partition", &hal_set_memory_partition,
         py::arg("index"), py::arg("mode"));
+  m.def("health_signals", &hal_health_signals, py::arg("index"),
+        "RAS counters, retired pages, temperatures and throttle flags of "
+        "one processor; refused reads are listed under 'unsupported'");
   m.def("lib_version", &hal_lib_version);
 }

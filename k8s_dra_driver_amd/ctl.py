@@ -9,6 +9,7 @@ projection, carve/restore partitions, and run the health probes.
     amd-dra-ctl slice                # ResourceSlice device JSON
     amd-dra-ctl partition 0 CPX NPS1 # dynamic repartition (needs idle GPU)
     amd-dra-ctl health               # per-GPU health + HIP probes
+    amd-dra-ctl health --signals     # + ECC / retired-page / thermal signals
 Use ``--hal fake`` anywhere to drive the modeled 8xMI355X node.
 """
 
@@ -130,21 +131,89 @@ def cmd_partition(args) -> int:
     return 0
 
 
+def _health_record(lib, g) -> dict:
+    """health_check + passive signals + one-shot policy for one GPU. A
+    single reading has no earlier poll to compare with, so growth-based
+    findings (UncorrectableEcc, CorrectableEccGrowth, DeferredEcc) can only
+    come from the running plugin; a non-zero uncorrectable count shows up
+    here as UncorrectableEccHistoric."""
+    from .plugin.health import HealthFinding, evaluate
+
+    h = lib.health_check(g.index)
+    findings = []
+    if h.get("status") != "healthy":
+        findings.append(
+            HealthFinding(
+                "HealthCheckFailed", "soft", f"status {h.get('status')!r}"
+            )
+        )
+    signals = None
+    try:
+        signals = lib.health_signals(g.index)
+        findings += evaluate(signals, None, signals)
+    except Exception as e:
+        findings.append(HealthFinding("HealthSignalsError", "soft", str(e)))
+    return {
+        "name": g.canonical_name,
+        "index": g.index,
+        "uuid": g.uuid,
+        "health": h,
+        "signals": {
+            k: v
+            for k, v in (signals.to_dict() if signals else {}).items()
+            if k != "unsupported" and v is not None
+        },
+        "unsupported": dict(signals.unsupported) if signals else {},
+        "findings": [
+            {"reason": f.reason, "severity": f.severity, "detail": f.detail}
+            for f in findings
+        ],
+    }
+
+
+def _print_signals(rec: dict) -> None:
+    for k, v in rec["signals"].items():
+        if k == "ecc_blocks":
+            for block, counts in sorted(v.items()):
+                print(
+                    f"    ecc_blocks.{block}: "
+                    + " ".join(f"{n}={c}" for n, c in sorted(counts.items()))
+                )
+        else:
+            print(f"    {k}: {v}")
+    for f in rec["findings"]:
+        print(f"    finding [{f['severity']}] {f['reason']}: {f['detail']}")
+    if not rec["findings"]:
+        print("    findings: none")
+    for k, why in sorted(rec["unsupported"].items()):
+        print(f"    unsupported {k}: {why}")
+
+
 def cmd_health(args) -> int:
     lib = _lib(args)
     rc = 0
+    records = []
     for g in lib.enumerate():
-        h = lib.health_check(g.index)
-        print(f"{g.canonical_name}: {h}")
-        if h.get("status") != "healthy":
+        rec = _health_record(lib, g)
+        records.append(rec)
+        if not args.json:
+            print(f"{g.canonical_name}: {rec['health']}")
+            if args.signals:
+                _print_signals(rec)
+        if any(f["severity"] in ("fatal", "soft") for f in rec["findings"]):
             rc = 1
+    if args.json:
+        print(json.dumps(records, indent=2, sort_keys=True))
     if args.probe:
         from . import _hiphealth
 
         for d in range(_hiphealth.device_count()):
             chk = _hiphealth.mfma_check(d)
             bw = _hiphealth.bandwidth_gbs(d, 256, 5)
-            print(f"hip:{d}: mfma_ok={chk['ok']} bandwidth={bw:.0f}GB/s")
+            print(
+                f"hip:{d}: mfma_ok={chk['ok']} bandwidth={bw:.0f}GB/s",
+                file=sys.stderr if args.json else sys.stdout,
+            )
             if not chk["ok"]:
                 rc = 1
     return rc
@@ -206,6 +275,15 @@ def main(argv=None) -> int:
     sub.add_parser("labels")
     hp = sub.add_parser("health")
     hp.add_argument("--probe", action="store_true", help="also run HIP kernels")
+    hp.add_argument(
+        "--signals",
+        action="store_true",
+        help="also print ECC / retired-page / thermal signals, findings "
+        "and the unsupported list",
+    )
+    hp.add_argument(
+        "--json", action="store_true", help="one JSON record per GPU"
+    )
     prof = sub.add_parser("profile")
     prof.add_argument("--host", default="127.0.0.1")
     prof.add_argument("--port", type=int, default=8083)

@@ -28,7 +28,7 @@ from typing import Dict, List, Optional
 
 from ..partition.catalog import COMPUTE_MODES, DEFAULT_VALID_NPS, make_profile
 from .base import DeviceLib, HalError, HalUnavailable
-from .model import GpuInfo, PartitionedDeviceInfo, XgmiLink
+from .model import GpuInfo, HealthSignals, PartitionedDeviceInfo, XgmiLink
 from .sysfs import KfdTopology
 
 log = logging.getLogger(__name__)
@@ -439,3 +439,12 @@ class AmdSmiDeviceLib(DeviceLib):
             "memoryPartition": g.memory_partition,
             "renderD": str(g.render_minor),
         }
+
+    def health_signals(self, gpu_index: int) -> HealthSignals:
+        """RAS / thermal telemetry of the GPU's primary (partition-0)
+        processor: RAS counters and sensors are per physical device, and
+        the partition-0 processor is the one AMD SMI answers them on."""
+        ext = self._require()
+        return HealthSignals.from_dict(
+            ext.health_signals(self._head_proc_index(gpu_index))
+        )

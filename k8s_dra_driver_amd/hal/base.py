@@ -19,7 +19,7 @@ from __future__ import annotations
 import abc
 from typing import Dict, List, Optional
 
-from .model import GpuInfo
+from .model import GpuInfo, HealthSignals
 
 
 class HalError(RuntimeError):
@@ -120,3 +120,13 @@ class DeviceLib(abc.ABC):
     @abc.abstractmethod
     def health_check(self, gpu_index: int) -> Dict[str, str]:
         """Lightweight liveness/metrics probe for failure detection."""
+
+    def health_signals(self, gpu_index: int) -> HealthSignals:
+        """Passive RAS / thermal telemetry (ECC counts, retired pages,
+        temperatures, throttle flags) the kernel driver already keeps.
+        Read-only and launch-free, so it is safe while tenants hold the
+        GPU. Polled by the health monitor only — never on the prepare
+        path. Backends without a source report everything unsupported."""
+        return HealthSignals.all_unsupported(
+            f"{type(self).__name__} has no health-signal source"
+        )

@@ -31,7 +31,13 @@ from ..partition.catalog import (
     validate_mode_combo,
 )
 from .base import DeviceLib, HalError, HalNotSupported
-from .model import GpuInfo, PartitionedDeviceInfo, XgmiLink
+from .model import (
+    HEALTH_SIGNAL_NAMES,
+    GpuInfo,
+    HealthSignals,
+    PartitionedDeviceInfo,
+    XgmiLink,
+)
 
 
 @dataclass
@@ -89,6 +95,32 @@ class _FakeGpuState:
         self.uuid = f"amd-mi355x-{index:02d}-{0xACE0 + index:04x}"
         self.oam_id = index
         self.busy_pids: List[int] = []  # processes holding the GPU
+        self.signals = _clean_signals()
+
+
+def _clean_signals() -> HealthSignals:
+    """A GPU with no RAS history, cool and unthrottled."""
+    return HealthSignals(
+        ecc_correctable=0,
+        ecc_uncorrectable=0,
+        ecc_deferred=0,
+        ecc_blocks={
+            "UMC": {"correctable": 0, "uncorrectable": 0, "deferred": 0}
+        },
+        bad_pages_reserved=0,
+        bad_pages_pending=0,
+        bad_pages_unreservable=0,
+        bad_page_threshold=128,
+        temp_hotspot_c=45.0,
+        temp_hotspot_crit_c=110.0,
+        temp_vram_c=40.0,
+        temp_vram_crit_c=105.0,
+        throttle_prochot=False,
+        throttle_ppt=False,
+        throttle_socket_thermal=False,
+        throttle_vr_thermal=False,
+        throttle_hbm_thermal=False,
+    )
 
 
 class FakeDeviceLib(DeviceLib):
@@ -314,3 +346,26 @@ class FakeDeviceLib(DeviceLib):
             "computePartition": g.compute_mode,
             "memoryPartition": g.memory_mode,
         }
+
+    def health_signals(self, gpu_index: int) -> HealthSignals:
+        self.faults.fire("health_signals")
+        self._check_open()
+        with self._lock:
+            return copy.deepcopy(self._gpus[gpu_index].signals)
+
+    def set_health_signals(self, gpu_index: int, **fields) -> None:
+        """Test helper: overwrite signal fields of one GPU, e.g.
+        ``set_health_signals(0, ecc_uncorrectable=3)``. ``None`` makes the
+        signal unsupported; ``reset=True`` first restores the clean state."""
+        with self._lock:
+            g = self._gpus[gpu_index]
+            if fields.pop("reset", False):
+                g.signals = _clean_signals()
+            for name, value in fields.items():
+                if name not in HEALTH_SIGNAL_NAMES:
+                    raise ValueError(f"unknown health signal {name!r}")
+                setattr(g.signals, name, value)
+                if value is None:
+                    g.signals.unsupported[name] = "unsupported (injected)"
+                else:
+                    g.signals.unsupported.pop(name, None)

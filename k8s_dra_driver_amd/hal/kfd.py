@@ -20,8 +20,8 @@ import os
 from typing import Dict, List, Optional
 
 from .base import DeviceLib, HalError, HalNotSupported, HalUnavailable
-from .model import GpuInfo, XgmiLink
-from .sysfs import KfdNode, KfdTopology
+from .model import GpuInfo, HealthSignals, XgmiLink
+from .sysfs import KfdNode, KfdTopology, read_health_signals
 
 log = logging.getLogger(__name__)
 
@@ -174,3 +174,11 @@ class KfdDeviceLib(DeviceLib):
             return {"status": "missing"}
         g = gpus[gpu_index]
         return {"status": "healthy", "uuid": g.uuid, "renderD": str(g.render_minor)}
+
+    def health_signals(self, gpu_index: int) -> HealthSignals:
+        gpus = self.enumerate()
+        if gpu_index >= len(gpus):
+            raise HalError(f"gpu-{gpu_index} not found")
+        return read_health_signals(
+            self.topology.root, gpus[gpu_index].render_minor
+        )

@@ -134,6 +134,94 @@ class GpuInfo:
         return sorted(l.peer_oam_id for l in self.links)
 
 
+#: every scalar health signal a backend reports, exactly once: as a value
+#: on :class:`HealthSignals` or as a key of its ``unsupported`` dict
+ECC_SIGNALS = ("ecc_correctable", "ecc_uncorrectable", "ecc_deferred")
+BAD_PAGE_SIGNALS = (
+    "bad_pages_reserved",
+    "bad_pages_pending",
+    "bad_pages_unreservable",
+)
+TEMP_SIGNALS = (
+    "temp_hotspot_c",
+    "temp_hotspot_crit_c",
+    "temp_vram_c",
+    "temp_vram_crit_c",
+)
+THROTTLE_SIGNALS = (
+    "throttle_prochot",
+    "throttle_ppt",
+    "throttle_socket_thermal",
+    "throttle_vr_thermal",
+    "throttle_hbm_thermal",
+)
+HEALTH_SIGNAL_NAMES = (
+    ECC_SIGNALS
+    + ("ecc_blocks",)
+    + BAD_PAGE_SIGNALS
+    + ("bad_page_threshold",)
+    + TEMP_SIGNALS
+    + THROTTLE_SIGNALS
+)
+
+
+@dataclass
+class HealthSignals:
+    """Passive RAS / thermal telemetry of one physical GPU, as the amdgpu
+    driver keeps it (nothing is launched on the device to obtain it).
+
+    ``None`` means the backend could not read the signal; the reason is in
+    ``unsupported`` under the field's name. An unsupported signal is never
+    a zero: policy must not mistake "cannot tell" for "clean". ECC counts
+    are accumulated since the driver was loaded; temperatures are Celsius.
+    """
+
+    ecc_correctable: Optional[int] = None
+    ecc_uncorrectable: Optional[int] = None
+    ecc_deferred: Optional[int] = None
+    #: block name -> {"correctable", "uncorrectable", "deferred"}; blocks
+    #: whose read was refused appear in ``unsupported`` as ecc_blocks.<NAME>
+    ecc_blocks: Optional[Dict[str, Dict[str, int]]] = None
+    bad_pages_reserved: Optional[int] = None
+    bad_pages_pending: Optional[int] = None
+    bad_pages_unreservable: Optional[int] = None
+    bad_page_threshold: Optional[int] = None
+    temp_hotspot_c: Optional[float] = None
+    temp_hotspot_crit_c: Optional[float] = None
+    temp_vram_c: Optional[float] = None
+    temp_vram_crit_c: Optional[float] = None
+    throttle_prochot: Optional[bool] = None
+    throttle_ppt: Optional[bool] = None
+    throttle_socket_thermal: Optional[bool] = None
+    throttle_vr_thermal: Optional[bool] = None
+    throttle_hbm_thermal: Optional[bool] = None
+    unsupported: Dict[str, str] = field(default_factory=dict)
+
+    @classmethod
+    def all_unsupported(cls, why: str) -> "HealthSignals":
+        return cls(unsupported={n: why for n in HEALTH_SIGNAL_NAMES})
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "HealthSignals":
+        """From the native binding's dict; a signal that is neither a value
+        nor listed as unsupported is recorded as unsupported."""
+        out = cls(unsupported=dict(d.get("unsupported") or {}))
+        for name in HEALTH_SIGNAL_NAMES:
+            if name in d and d[name] is not None:
+                setattr(out, name, d[name])
+            elif name not in out.unsupported:
+                out.unsupported[name] = "not reported"
+        return out
+
+    def to_dict(self) -> dict:
+        out = {n: getattr(self, n) for n in HEALTH_SIGNAL_NAMES}
+        out["unsupported"] = dict(self.unsupported)
+        return out
+
+    def active_throttles(self) -> List[str]:
+        return [n for n in THROTTLE_SIGNALS if getattr(self, n)]
+
+
 # ---------------------------------------------------------------------------
 # ResourceSlice Device projection (resource.k8s.io/v1beta1 JSON shape)
 # ---------------------------------------------------------------------------

@@ -93,6 +93,84 @@ class PluginMetrics:
             registry=self.registry,
         )
 
+        # Passive health signals (set by the health monitor's poll, never
+        # on the prepare path). An unsupported signal exports no sample.
+        self.gpu_ecc_errors = Gauge(
+            "dra_gpu_ecc_errors",
+            "Accumulated ECC error count since the amdgpu driver loaded",
+            ["gpu", "kind"],
+            registry=self.registry,
+        )
+        self.gpu_bad_pages = Gauge(
+            "dra_gpu_bad_pages",
+            "Retired (bad) VRAM pages by status",
+            ["gpu", "status"],
+            registry=self.registry,
+        )
+        self.gpu_temperature = Gauge(
+            "dra_gpu_temperature_celsius",
+            "GPU temperature by sensor",
+            ["gpu", "sensor"],
+            registry=self.registry,
+        )
+        self.gpu_unhealthy = Gauge(
+            "dra_gpu_unhealthy",
+            "1 while the GPU is marked unhealthy, labelled with the reason",
+            ["gpu", "reason"],
+            registry=self.registry,
+        )
+        self.gpu_health_warnings = Counter(
+            "dra_gpu_health_warnings_total",
+            "Health warnings raised (warnings never taint a GPU)",
+            ["gpu", "reason"],
+            registry=self.registry,
+        )
+        #: gpu label -> reason label currently exported as dra_gpu_unhealthy
+        self._unhealthy_reason = {}
+
+    @staticmethod
+    def _set_or_drop(gauge: Gauge, labels: tuple, value) -> None:
+        if value is None:
+            try:
+                gauge.remove(*labels)
+            except KeyError:
+                pass
+        else:
+            gauge.labels(*labels).set(value)
+
+    def observe_health(self, report) -> None:
+        """Export one GPU's poll (a plugin.health.PollReport)."""
+        gpu = str(report.gpu_index)
+        s = report.signals
+        if s is not None:
+            for kind in ("correctable", "uncorrectable", "deferred"):
+                self._set_or_drop(
+                    self.gpu_ecc_errors, (gpu, kind), getattr(s, f"ecc_{kind}")
+                )
+            for status in ("reserved", "pending", "unreservable"):
+                self._set_or_drop(
+                    self.gpu_bad_pages,
+                    (gpu, status),
+                    getattr(s, f"bad_pages_{status}"),
+                )
+            for sensor in ("hotspot", "vram"):
+                self._set_or_drop(
+                    self.gpu_temperature,
+                    (gpu, sensor),
+                    getattr(s, f"temp_{sensor}_c"),
+                )
+        for reason in report.new_warnings:
+            self.gpu_health_warnings.labels(gpu, reason).inc()
+        reason = (report.primary_reason or "Unknown") if report.unhealthy else ""
+        old = self._unhealthy_reason.get(gpu, "")
+        if old and old != reason:
+            self._set_or_drop(self.gpu_unhealthy, (gpu, old), None)
+        if reason:
+            self.gpu_unhealthy.labels(gpu, reason).set(1)
+            self._unhealthy_reason[gpu] = reason
+        else:
+            self._unhealthy_reason.pop(gpu, None)
+
     @contextlib.contextmanager
     def time_prepare(self):
         t0 = time.perf_counter()

@@ -16,6 +16,7 @@ errors, exactly like the reference (``driver.go:96-116``).
 from __future__ import annotations
 
 import logging
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
@@ -144,8 +145,13 @@ class Driver:
         from .health import HealthMonitor
 
         self.health = HealthMonitor(
-            lib, on_change=lambda _unhealthy: self.publish_resources()
+            lib,
+            on_change=self._on_health_change,
+            on_poll=self._on_health_poll,
         )
+        #: unhealthy set at the last change (to tell transitions apart)
+        self._last_unhealthy: set = set()
+        self._health_change_lock = threading.Lock()
         # Out-of-band shared-GPU isolation enforcement (sharing.go:211-221
         # analog): detect containers that stripped/altered their CU mask.
         self.enforcer = None
@@ -174,6 +180,44 @@ class Driver:
             f"pid {v.pid}: {v.kind} — {v.detail}"
             + (" (process killed)" if self.enforcer.action == "kill" else ""),
         )
+
+    def _on_health_change(self, unhealthy) -> None:
+        """Republish, and tell every claim holding a GPU that just turned
+        unhealthy — once per transition, not once per poll."""
+        with self._health_change_lock:
+            newly = set(unhealthy) - self._last_unhealthy
+            self._last_unhealthy = set(unhealthy)
+        self.publish_resources()
+        for gpu_index in sorted(newly):
+            reason = self.health.primary_reason(gpu_index)
+            detail = next(
+                (
+                    f.detail
+                    for f in self.health.findings(gpu_index)
+                    if f.reason == reason
+                ),
+                "",
+            )
+            for uid in self.state.ledger.holders(gpu_index):
+                try:
+                    pc = self.state.checkpoints.read(uid)
+                    info = ClaimRef(
+                        namespace=pc.namespace if pc else "default",
+                        name=pc.name if pc else uid,
+                        uid=uid,
+                    )
+                    self._emit_claim_warning(
+                        info,
+                        "DeviceUnhealthy",
+                        f"gpu-{gpu_index} is unhealthy"
+                        + (f": {reason}" if reason else "")
+                        + (f" ({detail})" if detail else ""),
+                    )
+                except Exception:
+                    log.exception("DeviceUnhealthy event for %s failed", uid)
+
+    def _on_health_poll(self, report) -> None:
+        self.metrics.observe_health(report)
 
     # ------------------------------------------------------------------
     def startup(self) -> None:
@@ -244,7 +288,11 @@ class Driver:
 
     def _taints_for(self, d) -> list:
         if d.parent_gpu.index in self.health.unhealthy_gpus:
-            return [dict(self.UNHEALTHY_TAINT)]
+            taint = dict(self.UNHEALTHY_TAINT)
+            reason = self.health.primary_reason(d.parent_gpu.index)
+            if reason:
+                taint["value"] = reason
+            return [taint]
         return []
 
     def publish_resources(self) -> None:
