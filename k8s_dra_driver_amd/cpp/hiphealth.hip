@@ -11,6 +11,8 @@
 //   mfma_tflops()    - bf16 MFMA throughput burn (8 independent
 //                      accumulators to cover the ~17 cyc/SIMD issue rate)
 //   burn_ms()        - VALU occupancy burner for time-slice/share demos
+//   *_probe()        - test hooks: one launch of a kernel above on the
+//                      caller's bytes, results returned between guards
 //
 // Written for gfx950: 64-wide waves, 256 CUs in 8 XCDs (grids sized
 // >> 256 workgroups), 16 B/lane streaming accesses.
@@ -180,8 +182,27 @@ __global__ void mfma_ones(float* out, int iters) {
   for (int r = 0; r < 4; ++r) out[base + r] = acc[r];
 }
 
+// One wave, no layout logic: lane l applies the instruction `iters` times
+// to the fragments it is handed (8 bf16 of a and b, 4 floats of c) and
+// stores its 4 accumulator floats. Which matrix element each slot holds is
+// the caller's business (tests/hip_reference.py), so a test can pin the
+// hardware's lane maps down with exact data.
+__global__ void __launch_bounds__(64) mfma_frag(
+    const bf16x8* __restrict__ a, const bf16x8* __restrict__ b,
+    const f32x4* __restrict__ c, f32x4* __restrict__ d, int iters) {
+  int lane = threadIdx.x;
+  bf16x8 fa = a[lane], fb = b[lane];
+  f32x4 acc = c[lane];
+  for (int i = 0; i < iters; ++i)
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc, 0, 0, 0);
+  d[lane] = acc;
+}
+
 // Throughput burn: 8 independent accumulators so back-to-back issue is not
-// dependency-limited (~17 cyc/SIMD issue for 16x16x32).
+// dependency-limited (~17 cyc/SIMD issue for 16x16x32). The timed instance
+// is <false>; <true> stores every thread's sum so a test can observe the
+// arithmetic (mfma_burn_probe).
+template <bool kStore>
 __global__ void __launch_bounds__(256, 4) mfma_burn(float* sink, int iters) {
   bf16x8 a, b;
 #pragma unroll
@@ -200,7 +221,10 @@ __global__ void __launch_bounds__(256, 4) mfma_burn(float* sink, int iters) {
   float s = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) s += acc[j][0] + acc[j][1] + acc[j][2] + acc[j][3];
-  if (s == -1.f) sink[blockIdx.x] = s;  // never true; defeats DCE
+  if constexpr (kStore)
+    sink[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = s;
+  else if (s == -1.f)
+    sink[blockIdx.x] = s;  // never true; defeats DCE
 }
 
 py::dict mfma_check(int device) {
@@ -234,13 +258,14 @@ double mfma_tflops(int device, int iters, int blocks) {
   float* sink = nullptr;
   HIP_CHECK(hipMalloc(&sink, blocks * sizeof(float)));
   dim3 grid(blocks), block(256);
-  hipLaunchKernelGGL(mfma_burn, grid, block, 0, 0, sink, 64);  // warmup
+  hipLaunchKernelGGL(mfma_burn<false>, grid, block, 0, 0, sink,
+                     64);  // warmup
   HIP_CHECK(hipDeviceSynchronize());
   hipEvent_t t0, t1;
   HIP_CHECK(hipEventCreate(&t0));
   HIP_CHECK(hipEventCreate(&t1));
   HIP_CHECK(hipEventRecord(t0));
-  hipLaunchKernelGGL(mfma_burn, grid, block, 0, 0, sink, iters);
+  hipLaunchKernelGGL(mfma_burn<false>, grid, block, 0, 0, sink, iters);
   HIP_CHECK(hipEventRecord(t1));
   HIP_CHECK(hipEventSynchronize(t1));
   float ms = 0;
@@ -260,6 +285,14 @@ double mfma_tflops(int device, int iters, int blocks) {
 // all-pairs gravitation, bodies tiled through LDS so each position is
 // fetched from HBM once per tile instead of once per pair.
 // ---------------------------------------------------------------------------
+
+// kSoftened promises softening2 > 0, so r2 > 0 for every pair. Without
+// softening a body's term with itself has r2 = 0: rsqrt gives inf and
+// inf * 0 a NaN in every acceleration. <false> gives a pair at distance
+// zero no force instead. The select costs 8% of the softened rate at 65536
+// bodies on an MI355X (3% as an fminf clamp), so it is compiled only into
+// the instance that needs it.
+template <bool kSoftened>
 __global__ void __launch_bounds__(256) nbody_step(
     const float4* __restrict__ pos_in, float4* __restrict__ pos_out,
     float4* __restrict__ vel, int n, float dt, float softening2) {
@@ -280,6 +313,7 @@ __global__ void __launch_bounds__(256) nbody_step(
       float dz = other.z - my.z;
       float r2 = dx * dx + dy * dy + dz * dz + softening2;
       float inv_r = __frsqrt_rn(r2);
+      if constexpr (!kSoftened) inv_r = r2 == 0.f ? 0.f : inv_r;
       float f = other.w * inv_r * inv_r * inv_r;  // m / r^3
       ax = fmaf(f, dx, ax);
       ay = fmaf(f, dy, ay);
@@ -326,8 +360,8 @@ py::list nbody_positions(int device, int num_bodies, int iters, int sample) {
   dim3 block(256), grid(n / 256);
   const float dt = 1e-3f, soft2 = 1e-4f;
   for (int i = 0; i < iters; ++i) {
-    hipLaunchKernelGGL(nbody_step, grid, block, 0, 0, pos_a, pos_b, vel, n,
-                       dt, soft2);
+    hipLaunchKernelGGL(nbody_step<true>, grid, block, 0, 0, pos_a, pos_b,
+                       vel, n, dt, soft2);
     std::swap(pos_a, pos_b);
   }
   HIP_CHECK(hipDeviceSynchronize());
@@ -366,16 +400,16 @@ py::dict nbody_benchmark(int device, int num_bodies, int iters) {
   HIP_CHECK(hipMemset(vel, 0, bytes));
   dim3 block(256), grid(n / 256);
   const float dt = 1e-3f, soft2 = 1e-4f;
-  hipLaunchKernelGGL(nbody_step, grid, block, 0, 0, pos_a, pos_b, vel, n,
-                     dt, soft2);  // warmup
+  hipLaunchKernelGGL(nbody_step<true>, grid, block, 0, 0, pos_a, pos_b, vel,
+                     n, dt, soft2);  // warmup
   HIP_CHECK(hipDeviceSynchronize());
   hipEvent_t t0, t1;
   HIP_CHECK(hipEventCreate(&t0));
   HIP_CHECK(hipEventCreate(&t1));
   HIP_CHECK(hipEventRecord(t0));
   for (int i = 0; i < iters; ++i) {
-    hipLaunchKernelGGL(nbody_step, grid, block, 0, 0, pos_a, pos_b, vel, n,
-                       dt, soft2);
+    hipLaunchKernelGGL(nbody_step<true>, grid, block, 0, 0, pos_a, pos_b,
+                       vel, n, dt, soft2);
     std::swap(pos_a, pos_b);
   }
   HIP_CHECK(hipEventRecord(t1));
@@ -435,6 +469,176 @@ double burn_ms(int device, int millis) {
 }
 
 // ---------------------------------------------------------------------------
+// test hooks: run the kernels above once on caller-supplied bytes and hand
+// the raw results back (tests/test_hip_kernels.py). Every argument is
+// validated before the first allocation or launch. Every device buffer a
+// kernel touches sits between two kGuard-byte guards; guards and outputs
+// are pre-filled with kCanary and results are returned guards included, so
+// an off-by-one access lands in a guard and shows as a changed byte. The
+// guards of a buffer that is only read hold kInputGuard instead: an element
+// read past the end of an input and stored past the end of an output would
+// otherwise put a canary on a canary.
+// ---------------------------------------------------------------------------
+constexpr size_t kGuard = 4096;  // multiple of 16: payloads stay float4-aligned
+constexpr int kCanary = 0xA5;
+constexpr int kInputGuard = 0x5A;
+constexpr size_t kProbeMaxBytes = (size_t)64 << 20;
+constexpr int kProbeMaxBlocks = 4096;
+constexpr int kProbeMaxIters = 1 << 16;
+
+void probe_device(int device) {
+  int count = 0;
+  HIP_CHECK(hipGetDeviceCount(&count));
+  if (device < 0 || device >= count)
+    throw std::invalid_argument("device " + std::to_string(device) +
+                                " out of range (" + std::to_string(count) +
+                                " visible)");
+  HIP_CHECK(hipSetDevice(device));
+}
+
+void probe_range(const char* what, long long v, long long lo, long long hi) {
+  if (v < lo || v > hi)
+    throw std::invalid_argument(std::string(what) + " must be in [" +
+                                std::to_string(lo) + ", " +
+                                std::to_string(hi) + "], got " +
+                                std::to_string(v));
+}
+
+// guard | payload | guard on the device, all `fill` unless `init` supplies
+// the payload. Freed on scope exit, also when a later call throws.
+class GuardedBuf {
+ public:
+  explicit GuardedBuf(size_t bytes, const void* init = nullptr,
+                      int fill = kCanary)
+      : bytes_(bytes) {
+    HIP_CHECK(hipMalloc(&base_, total()));
+    try {
+      HIP_CHECK(hipMemset(base_, fill, total()));
+      if (init && bytes_)
+        HIP_CHECK(hipMemcpy(base_ + kGuard, init, bytes_,
+                            hipMemcpyHostToDevice));
+    } catch (...) {
+      (void)hipFree(base_);
+      throw;
+    }
+  }
+  GuardedBuf(const GuardedBuf&) = delete;
+  GuardedBuf& operator=(const GuardedBuf&) = delete;
+  ~GuardedBuf() { (void)hipFree(base_); }
+
+  size_t total() const { return bytes_ + 2 * kGuard; }
+  template <typename T>
+  T* payload() const {
+    return reinterpret_cast<T*>(base_ + kGuard);
+  }
+  py::bytes download() const {
+    std::string host(total(), '\0');
+    HIP_CHECK(hipMemcpy(&host[0], base_, total(), hipMemcpyDeviceToHost));
+    return py::bytes(host);
+  }
+
+ private:
+  char* base_ = nullptr;
+  size_t bytes_;
+};
+
+py::bytes copy_probe(int device, const py::bytes& src_bytes,
+                     const std::string& variant, int blocks) {
+  std::string src = src_bytes;
+  void (*kernel)(const float4*, float4*, size_t) = nullptr;
+  if (variant == "plain")
+    kernel = copy_f4;
+  else if (variant == "nt")
+    kernel = copy_f4_nt;
+  else if (variant == "nt_u4")
+    kernel = copy_f4_nt_u4;
+  else
+    throw std::invalid_argument("variant must be plain, nt or nt_u4, got '" +
+                                variant + "'");
+  if (src.size() % sizeof(float4) != 0)
+    throw std::invalid_argument("len(src) must be a multiple of 16");
+  probe_range("len(src)", (long long)src.size(), 0, kProbeMaxBytes);
+  probe_range("blocks", blocks, 1, kProbeMaxBlocks);
+  probe_device(device);
+  size_t n = src.size() / sizeof(float4);
+  GuardedBuf s(src.size(), src.data(), kInputGuard);
+  GuardedBuf d(src.size());
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, 0,
+                     s.payload<const float4>(), d.payload<float4>(), n);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  return d.download();
+}
+
+py::tuple nbody_step_probe(int device, const py::bytes& pos_bytes,
+                           const py::bytes& vel_bytes, float dt,
+                           float softening2) {
+  std::string pos = pos_bytes, vel = vel_bytes;
+  if (pos.size() % sizeof(float4) != 0)
+    throw std::invalid_argument("len(pos) must be a multiple of 16");
+  if (vel.size() != pos.size())
+    throw std::invalid_argument("pos and vel must have the same length");
+  probe_range("len(pos)", (long long)pos.size(), 0, kProbeMaxBytes);
+  if (!std::isfinite(dt))
+    throw std::invalid_argument("dt must be finite");
+  if (!std::isfinite(softening2) || softening2 < 0.f)
+    throw std::invalid_argument("softening2 must be finite and >= 0");
+  probe_device(device);
+  int n = (int)(pos.size() / sizeof(float4));  // exactly as given
+  GuardedBuf p_in(pos.size(), pos.data(), kInputGuard);
+  GuardedBuf p_out(pos.size());
+  GuardedBuf v(vel.size(), vel.data());
+  if (n > 0) {
+    // a softening too small to be a normal float may be flushed to zero
+    // in the kernel, so it counts as none
+    auto kernel = std::isnormal(softening2) ? nbody_step<true>
+                                            : nbody_step<false>;
+    hipLaunchKernelGGL(kernel, dim3((n + 255) / 256), dim3(256), 0, 0,
+                       p_in.payload<const float4>(), p_out.payload<float4>(),
+                       v.payload<float4>(), n, dt, softening2);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  return py::make_tuple(p_out.download(), v.download());
+}
+
+py::bytes mfma_frag_probe(int device, const py::bytes& a_bytes,
+                          const py::bytes& b_bytes, const py::bytes& c_bytes,
+                          int iters) {
+  std::string a = a_bytes, b = b_bytes, c = c_bytes;
+  if (a.size() != 64 * sizeof(bf16x8))
+    throw std::invalid_argument("a must be 64x8 uint16 (1024 bytes)");
+  if (b.size() != 64 * sizeof(bf16x8))
+    throw std::invalid_argument("b must be 64x8 uint16 (1024 bytes)");
+  if (c.size() != 64 * sizeof(f32x4))
+    throw std::invalid_argument("c must be 64x4 float32 (1024 bytes)");
+  probe_range("iters", iters, 0, kProbeMaxIters);
+  probe_device(device);
+  GuardedBuf da(a.size(), a.data(), kInputGuard);
+  GuardedBuf db(b.size(), b.data(), kInputGuard);
+  GuardedBuf dc(c.size(), c.data(), kInputGuard);
+  GuardedBuf dd(c.size());
+  hipLaunchKernelGGL(mfma_frag, dim3(1), dim3(64), 0, 0,
+                     da.payload<const bf16x8>(), db.payload<const bf16x8>(),
+                     dc.payload<const f32x4>(), dd.payload<f32x4>(), iters);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  return dd.download();
+}
+
+py::bytes mfma_burn_probe(int device, int iters, int blocks) {
+  probe_range("iters", iters, 0, kProbeMaxIters);
+  probe_range("blocks", blocks, 1, kProbeMaxBlocks);
+  probe_device(device);
+  GuardedBuf out((size_t)blocks * 256 * sizeof(float));
+  hipLaunchKernelGGL(mfma_burn<true>, dim3(blocks), dim3(256), 0, 0,
+                     out.payload<float>(), iters);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  return out.download();
+}
+
+// ---------------------------------------------------------------------------
 // device info
 // ---------------------------------------------------------------------------
 int device_count() {
@@ -478,4 +682,25 @@ PYBIND11_MODULE(_hiphealth, m) {
         "Body positions after iters steps (CPU cross-check hook)");
   m.def("nbody_benchmark", &nbody_benchmark, py::arg("device") = 0,
         py::arg("num_bodies") = 65536, py::arg("iters") = 10);
+  m.attr("PROBE_GUARD_BYTES") = kGuard;
+  m.attr("PROBE_CANARY") = kCanary;
+  m.def("copy_probe", &copy_probe, py::arg("device"), py::arg("src"),
+        py::arg("variant"), py::arg("blocks"),
+        "One launch of copy_f4 ('plain'), copy_f4_nt ('nt') or "
+        "copy_f4_nt_u4 ('nt_u4') with grid=blocks, block=256 over "
+        "len(src)/16 float4; returns guard + dst + guard");
+  m.def("nbody_step_probe", &nbody_step_probe, py::arg("device"),
+        py::arg("pos"), py::arg("vel"), py::arg("dt"),
+        py::arg("softening2"),
+        "One nbody_step over exactly len(pos)/16 bodies (mass in pos.w); "
+        "returns (pos_out, vel_out), each with its guards");
+  m.def("mfma_frag_probe", &mfma_frag_probe, py::arg("device"),
+        py::arg("a"), py::arg("b"), py::arg("c"), py::arg("iters"),
+        "One wave: lane l applies v_mfma_f32_16x16x32_bf16 iters times to "
+        "its 8 bf16 of a and b and its 4 floats of c; returns "
+        "guard + 64x4 float32 + guard");
+  m.def("mfma_burn_probe", &mfma_burn_probe, py::arg("device"),
+        py::arg("iters"), py::arg("blocks"),
+        "mfma_burn with every thread's final sum stored; returns "
+        "guard + blocks*256 float32 + guard");
 }

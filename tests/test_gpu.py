@@ -455,6 +455,7 @@ class TestNbodyCorrectness:
                 0.5
             )
         pos = vals.reshape(n, 3).astype(np.float32)
+        p0 = pos[:sample].astype(np.float64)
         mass = np.full(n, 1.0 / n, dtype=np.float32)
         vel = np.zeros_like(pos)
         dt, soft2 = np.float32(1e-3), np.float32(1e-4)
@@ -469,6 +470,28 @@ class TestNbodyCorrectness:
         err = np.abs(gpu - ref).max()
         scale = np.abs(ref).max()
         assert err / scale < 1e-3, (err, scale)
+
+        # The bodies move by only ~7e-5 of the scale in these 3 steps, so
+        # the assertion above also holds for a kernel that copies its
+        # input. Hold the displacement against a float64 integration: the
+        # error budget is half an ulp of a position below 0.5 (2^-25) per
+        # step, times 4; the displacement itself is ~3.5e-5, a hundred
+        # times that.
+        import hip_reference
+
+        bodies = hip_reference.lcg_bodies(n)
+        assert np.array_equal(bodies[:sample, :3].astype(np.float64), p0)
+        p64 = bodies.astype(np.float64)
+        v64 = np.zeros((n, 3))
+        for _ in range(iters):
+            v64, x64, _ = hip_reference.nbody_ref64(p64, v64, dt, soft2)
+            p64 = np.concatenate([x64, p64[:, 3:]], axis=1)
+        p_ref = p64[:sample, :3]
+        disp_err = np.abs((gpu.astype(np.float64) - p0) - (p_ref - p0)).max()
+        assert disp_err <= 4 * iters * 2.0**-25, (
+            disp_err,
+            np.abs(p_ref - p0).max(),
+        )
 
 
 class TestProspectivePartitionsOnHardware:
