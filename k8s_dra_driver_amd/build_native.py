@@ -98,9 +98,12 @@ def build_amdhal_asan(force: bool = False) -> str:
 
 
 def build_hiphealth(force: bool = False) -> str:
+    """HIP kernels; rebuilt when the source or the self-test header it
+    includes changes."""
     src = os.path.join(CPP_DIR, "hiphealth.hip")
+    hdr = os.path.join(CPP_DIR, "selftest_kernels.hpp")
     out = os.path.join(PKG_DIR, f"_hiphealth{_ext_suffix()}")
-    if force or _needs_build(src, out):
+    if force or _needs_build(src, out) or _needs_build(hdr, out):
         hipcc = os.path.join(ROCM, "bin", "hipcc")
         if not os.path.exists(hipcc):
             hipcc = "hipcc"

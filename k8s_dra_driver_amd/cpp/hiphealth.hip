@@ -13,6 +13,9 @@
 //   burn_ms()        - VALU occupancy burner for time-slice/share demos
 //   *_probe()        - test hooks: one launch of a kernel above on the
 //                      caller's bytes, results returned between guards
+//   selftest()       - startup self-test: HBM fill/verify with four
+//                      patterns and an MFMA known-answer test
+//                      (selftest_kernels.hpp)
 //
 // Written for gfx950: 64-wide waves, 256 CUs in 8 XCDs (grids sized
 // >> 256 workgroups), 16 B/lane streaming accesses.
@@ -639,6 +642,11 @@ py::bytes mfma_burn_probe(int device, int iters, int blocks) {
 }
 
 // ---------------------------------------------------------------------------
+// startup self-test: HBM pattern test + MFMA known-answer test
+// ---------------------------------------------------------------------------
+#include "selftest_kernels.hpp"
+
+// ---------------------------------------------------------------------------
 // device info
 // ---------------------------------------------------------------------------
 int device_count() {
@@ -703,4 +711,32 @@ PYBIND11_MODULE(_hiphealth, m) {
         py::arg("iters"), py::arg("blocks"),
         "mfma_burn with every thread's final sum stored; returns "
         "guard + blocks*256 float32 + guard");
+  m.attr("SELFTEST_MAX_RECORDS") = kMaxRecords;
+  m.attr("SELFTEST_KAT_VECTORS") = kKatVectors;
+  m.def("selftest", &selftest, py::arg("device") = 0, py::arg("mib") = 1024,
+        py::arg("seed") = 0x5E1F7E57C0FFEEull, py::arg("blocks") = 0,
+        "Startup self-test: one region of mib MiB is filled and verified "
+        "with addr, addr_inv, hash and hash_inv (grid=blocks, 0 = 1024), "
+        "then mfma_kat runs on 4 blocks per CU. Returns {ok, device, seed, "
+        "bytes, memory: [{pattern, mismatches, records: [(word, got, "
+        "want)], fill_gbs, verify_gbs}], mfma: {blocks, checked, "
+        "mismatches, records: [(wave, lane, slot, got_bits, want_bits)]}}; "
+        "the GB/s figures are event-timed and informative only");
+  m.def("memtest_probe", &memtest_probe, py::arg("device"), py::arg("nbytes"),
+        py::arg("pattern"), py::arg("seed"), py::arg("blocks"),
+        py::arg("flips"), py::arg("stage"),
+        "mem_fill<pattern> over nbytes/16 elements with grid=blocks; with "
+        "stage='verify' every (word_index, mask) of flips is then XORed "
+        "into the region and mem_verify<pattern> runs. Returns "
+        "(guard + region + guard, mismatch count, first 64 records "
+        "(word, got, want))");
+  m.def("mfma_kat_probe", &mfma_kat_probe, py::arg("device"),
+        py::arg("a_tab"), py::arg("b_tab"), py::arg("c_tab"),
+        py::arg("want_tab"), py::arg("blocks"),
+        "mfma_kat on the caller's 16-vector table (a, b: 16x64x8 uint16; c, "
+        "want: 16x64x4 float32) with grid=blocks; returns (mismatch count, "
+        "first 64 records (wave, lane, slot, got_bits, want_bits), floats "
+        "compared)");
+  m.def("pci_bus_id", &pci_bus_id, py::arg("device") = 0,
+        "PCI address (domain:bus:device.function) of a HIP device");
 }

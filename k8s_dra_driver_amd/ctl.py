@@ -10,6 +10,7 @@ projection, carve/restore partitions, and run the health probes.
     amd-dra-ctl partition 0 CPX NPS1 # dynamic repartition (needs idle GPU)
     amd-dra-ctl health               # per-GPU health + HIP probes
     amd-dra-ctl health --signals     # + ECC / retired-page / thermal signals
+    amd-dra-ctl health --selftest    # + HBM pattern / MFMA known-answer test
 Use ``--hal fake`` anywhere to drive the modeled 8xMI355X node.
 """
 
@@ -189,17 +190,53 @@ def _print_signals(rec: dict) -> None:
         print(f"    unsupported {k}: {why}")
 
 
+def _selftest_into(rec: dict, g, mib: int) -> None:
+    """Self-test one GPU in a child process and add what it found to the
+    GPU's record. The operator vouches that nothing is using the GPU; a
+    partitioned GPU, or one without a PCI address, is skipped."""
+    from . import selftest
+
+    if g.compute_partition.upper() != "SPX" or g.partitions or not g.pcie_bdf:
+        rec["selftest"] = {"result": "skipped"}
+        return
+    res = selftest.run(g, mib=mib)
+    rec["selftest"] = {
+        "result": res.outcome,
+        "seconds": round(res.seconds, 3),
+        "mib": mib,
+    }
+    rec["findings"] += [
+        {"reason": f.reason, "severity": f.severity, "detail": f.detail}
+        for f in res.findings()
+    ]
+
+
 def cmd_health(args) -> int:
     lib = _lib(args)
     rc = 0
     records = []
     for g in lib.enumerate():
         rec = _health_record(lib, g)
+        if args.selftest:
+            _selftest_into(rec, g, args.selftest_mib)
         records.append(rec)
         if not args.json:
             print(f"{g.canonical_name}: {rec['health']}")
             if args.signals:
                 _print_signals(rec)
+            if args.selftest:
+                st = rec["selftest"]
+                print(
+                    f"    selftest: {st['result']}"
+                    + (f" ({st['seconds']:.1f}s)" if "seconds" in st else "")
+                )
+                if not args.signals:
+                    for f in rec["findings"]:
+                        if f["reason"].startswith("Selftest"):
+                            print(
+                                f"    finding [{f['severity']}] "
+                                f"{f['reason']}: {f['detail']}"
+                            )
         if any(f["severity"] in ("fatal", "soft") for f in rec["findings"]):
             rc = 1
     if args.json:
@@ -280,6 +317,19 @@ def main(argv=None) -> int:
         action="store_true",
         help="also print ECC / retired-page / thermal signals, findings "
         "and the unsupported list",
+    )
+    hp.add_argument(
+        "--selftest",
+        action="store_true",
+        help="also fill and verify HBM with known patterns and run the MFMA "
+        "known-answer test, one GPU at a time in a child process; only for "
+        "GPUs that nothing is using",
+    )
+    hp.add_argument(
+        "--selftest-mib",
+        type=int,
+        default=1024,
+        help="HBM region to test per GPU (default 1024)",
     )
     hp.add_argument(
         "--json", action="store_true", help="one JSON record per GPU"

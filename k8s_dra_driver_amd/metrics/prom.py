@@ -125,6 +125,20 @@ class PluginMetrics:
             ["gpu", "reason"],
             registry=self.registry,
         )
+        # Startup self-test (Driver.run_startup_selftest)
+        self.gpu_selftest_runs = Counter(
+            "dra_gpu_selftest_runs_total",
+            "Startup self-tests by result "
+            "(pass, memory, compute, error, skipped)",
+            ["gpu", "result"],
+            registry=self.registry,
+        )
+        self.gpu_selftest_seconds = Gauge(
+            "dra_gpu_selftest_seconds",
+            "Wall time of the GPU's last startup self-test",
+            ["gpu"],
+            registry=self.registry,
+        )
         #: gpu label -> reason label currently exported as dra_gpu_unhealthy
         self._unhealthy_reason = {}
 

@@ -220,6 +220,69 @@ class Driver:
         self.metrics.observe_health(report)
 
     # ------------------------------------------------------------------
+    def run_startup_selftest(
+        self, runner=None, *, mib: int = 1024, timeout_s: float = 120.0
+    ) -> Dict[int, str]:
+        """Self-test every GPU in scope that nothing is using, one after
+        another, and hand the findings to the health monitor. Meant for
+        one moment only: between construction and :meth:`startup`, when no
+        slice is published and no gRPC server exists, so nothing can start
+        using a GPU while it is tested. Returns ``{gpu index: result}``
+        with result in pass | memory | compute | error | skipped.
+
+        A GPU is skipped (logged, no finding) when a claim recovered from
+        the checkpoints holds it, when it is partitioned, or when it has
+        no PCI address to find it by."""
+        if runner is None:
+            from .. import selftest
+
+            runner = selftest.run
+        results: Dict[int, str] = {}
+        for gpu in self.lib.enumerate():
+            idx = gpu.index
+            if self.gpu_indices is not None and idx not in self.gpu_indices:
+                continue
+            holders = self.state.ledger.holders(idx)
+            if holders:
+                why = f"held by {len(holders)} recovered claim(s)"
+            elif gpu.compute_partition.upper() != "SPX" or gpu.partitions:
+                why = f"partitioned ({gpu.compute_partition})"
+            elif not gpu.pcie_bdf:
+                why = "no PCI address reported"
+            else:
+                why = ""
+            if why:
+                log.info("gpu-%d: startup self-test skipped: %s", idx, why)
+                results[idx] = "skipped"
+                self.metrics.gpu_selftest_runs.labels(str(idx), "skipped").inc()
+                continue
+            t0 = time.perf_counter()
+            try:
+                res = runner(gpu, mib=mib, timeout_s=timeout_s)
+                outcome, findings = res.outcome, res.findings()
+            except Exception as e:
+                log.exception("gpu-%d: startup self-test failed to run", idx)
+                from .health import HealthFinding, SOFT
+
+                outcome = "error"
+                findings = [HealthFinding("SelftestError", SOFT, str(e))]
+            seconds = time.perf_counter() - t0
+            results[idx] = outcome
+            self.metrics.gpu_selftest_runs.labels(str(idx), outcome).inc()
+            self.metrics.gpu_selftest_seconds.labels(str(idx)).set(seconds)
+            self.health.set_selftest_findings(idx, findings)
+            if findings:
+                for f in findings:
+                    log.error(
+                        "gpu-%d: startup self-test: %s: %s", idx, f.reason, f.detail
+                    )
+            else:
+                log.info(
+                    "gpu-%d: startup self-test passed in %.1fs", idx, seconds
+                )
+        self.health.check_once()
+        return results
+
     def startup(self) -> None:
         """Write the base CDI spec and publish ResourceSlices
         (reference main.go:167-206 + driver.go:70-84)."""

@@ -10,6 +10,8 @@ retry loops). This monitor:
 - on failure, excludes that GPU's devices from publication and republishes
   (scheduler stops placing new claims there),
 - on recovery, re-includes them,
+- carries the findings of the startup self-test (sticky: they hold until
+  they are replaced, see :meth:`HealthMonitor.set_selftest_findings`),
 - exposes state for metrics and node conditions.
 
 The signals are the telemetry the amdgpu driver already keeps (ECC counts,
@@ -42,10 +44,14 @@ REASONS: Tuple[Tuple[str, str], ...] = (
     ("BadPagesPending", FATAL),
     ("BadPageUnreservable", FATAL),
     ("BadPageThreshold", FATAL),
+    # raised by the startup self-test (k8s_dra_driver_amd.selftest)
+    ("SelftestMemoryMismatch", FATAL),
+    ("SelftestComputeMismatch", FATAL),
     ("ThermalCritical", SOFT),
     # raised by the monitor itself, not by evaluate()
     ("HealthCheckFailed", SOFT),
     ("HealthSignalsError", SOFT),
+    ("SelftestError", SOFT),
     ("UncorrectableEccHistoric", WARNING),
     ("CorrectableEccGrowth", WARNING),
     ("DeferredEcc", WARNING),
@@ -219,6 +225,8 @@ class HealthMonitor:
         #: why each unhealthy GPU is unhealthy (kept until it recovers)
         self._reasons: Dict[int, str] = {}
         self._logged_unsupported: Set[Tuple[int, str]] = set()
+        #: sticky self-test findings per GPU, added to every poll
+        self._selftest: Dict[int, List[HealthFinding]] = {}
         self._stop = threading.Event()
         self._thread: Optional[threading.Thread] = None
         self._lock = threading.Lock()
@@ -247,6 +255,20 @@ class HealthMonitor:
             if gpu_index not in self._unhealthy:
                 return ""
             return self._reasons.get(gpu_index, "")
+
+    def set_selftest_findings(
+        self, gpu_index: int, findings: List[HealthFinding]
+    ) -> None:
+        """Findings of an active self-test of one GPU. No poll can observe
+        them again, so they are sticky: every poll adds them to what it
+        found itself until the next call replaces them; an empty list
+        clears them. They take effect on the next poll, by the usual rules
+        (fatal at once, soft after ``failures_to_unhealthy`` polls)."""
+        with self._lock:
+            if findings:
+                self._selftest[gpu_index] = list(findings)
+            else:
+                self._selftest.pop(gpu_index, None)
 
     # ------------------------------------------------------------------
     def _read(self, gpu_index: int):
@@ -312,7 +334,9 @@ class HealthMonitor:
             with self._lock:
                 for idx, signals, extra in readings:
                     found = _sorted(
-                        self._evaluate_locked(idx, signals) + extra
+                        self._evaluate_locked(idx, signals)
+                        + extra
+                        + self._selftest.get(idx, [])
                     )
                     before = {
                         f.reason

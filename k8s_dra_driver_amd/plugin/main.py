@@ -131,6 +131,27 @@ def build_parser() -> argparse.ArgumentParser:
         "or alter their CU mask: warn = Warning event + metric, kill = "
         "SIGKILL the offending process (sharing.go:211-221 parity)",
     )
+    p.add_argument(
+        "--startup-selftest",
+        default=_env("STARTUP_SELFTEST", "off"),
+        choices=["off", "on"],
+        help="before the first publication, run the HBM pattern and MFMA "
+        "known-answer self-test on every GPU that no recovered claim holds; "
+        "a GPU that fails is published tainted",
+    )
+    p.add_argument(
+        "--selftest-mib",
+        type=int,
+        default=int(_env("SELFTEST_MIB", "1024")),
+        help="HBM region the self-test fills and verifies, per GPU (at or "
+        "below 256 the region may never leave the Infinity Cache)",
+    )
+    p.add_argument(
+        "--selftest-timeout-s",
+        type=float,
+        default=float(_env("SELFTEST_TIMEOUT_S", "120")),
+        help="kill one GPU's self-test after this long (SelftestError)",
+    )
     p.add_argument("-v", "--verbosity", type=int, default=int(_env("LOG_LEVEL", "1")))
     p.add_argument(
         "--logging-format",
@@ -153,11 +174,41 @@ def make_kube_client(args):
     )
 
 
+def require_selftest_extension(args) -> None:
+    """--startup-selftest on needs the built HIP extension. Without this
+    check every GPU's test would end in SelftestError and a missing build
+    would look like a sick fleet."""
+    if args.startup_selftest != "on":
+        return
+    from .. import selftest
+
+    if not selftest.extension_path():
+        raise RuntimeError(
+            "--startup-selftest on: the _hiphealth extension is not built "
+            f"(nothing like _hiphealth*.so in {selftest.PKG_DIR}); build it "
+            "(python -m k8s_dra_driver_amd.build_native) or turn the "
+            "self-test off"
+        )
+
+
+def startup_selftest(args, driver) -> bool:
+    """Run the startup self-test when the flag asks for it; True if it ran.
+    Called between Driver(...) and driver.startup(), so the first published
+    slice already carries the taint of a GPU that failed."""
+    if args.startup_selftest != "on":
+        return False
+    driver.run_startup_selftest(
+        mib=args.selftest_mib, timeout_s=args.selftest_timeout_s
+    )
+    return True
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     from ..utils.log import setup_logging
 
     setup_logging(args.verbosity, json_format=args.logging_format == "json")
+    require_selftest_extension(args)
     lib = new_device_lib(args.hal)
     lib.open()
     kube = make_kube_client(args)
@@ -188,6 +239,7 @@ def main(argv=None) -> int:
             else None
         ),
     )
+    startup_selftest(args, driver)
     driver.startup()
     driver.health.start()  # failure detection -> slice self-healing
     if driver.enforcer is not None:

@@ -1,0 +1,279 @@
+"""Startup GPU self-test: write known data to HBM, read it back, and compute
+a known answer on the matrix pipes, before the GPU is offered to anybody.
+
+The passive signals of ``plugin/health.py`` only listen to what the amdgpu
+driver counts. This is the active counterpart, deliberately narrow: it runs
+on a GPU that nothing is using, at a moment when nothing can start using it
+(plugin startup, before the first publication), or when an operator asks
+for it (``amd-dra-ctl health --selftest``).
+
+Two halves:
+
+- **child** (``python -m k8s_dra_driver_amd.selftest --bdf B --mib N
+  --json``): finds the HIP device with that PCI address, runs
+  ``_hiphealth.selftest`` on it and prints one JSON object. Exit 0 = passed,
+  1 = mismatches found, 2 = could not run. Imports neither torch nor the
+  plugin.
+- **parent** (:func:`run`): starts that child in a fresh process with a
+  timeout, one child at a time, and turns what it says into a
+  :class:`SelftestResult`. The calling process never initialises HIP, so a
+  hung or crashed test cannot take the plugin with it.
+"""
+
+from __future__ import annotations
+
+import argparse
+import importlib.machinery
+import json
+import os
+import subprocess
+import sys
+import threading
+import time
+from dataclasses import dataclass
+from typing import Callable, List, Optional, Tuple
+
+PKG_DIR = os.path.dirname(os.path.abspath(__file__))
+
+DEFAULT_MIB = 1024
+DEFAULT_TIMEOUT_S = 120.0
+
+EXIT_PASS = 0
+EXIT_MISMATCH = 1
+EXIT_ERROR = 2
+
+#: spawn(argv, timeout_s) -> (returncode, stdout, stderr); raises
+#: subprocess.TimeoutExpired when the child had to be killed
+Spawn = Callable[[List[str], float], Tuple[int, str, str]]
+
+
+def extension_path() -> str:
+    """The built ``_hiphealth`` extension as a file, "" when it is missing
+    (looked for, not imported: importing it initialises nothing, but the
+    plugin has no business loading HIP)."""
+    for suffix in importlib.machinery.EXTENSION_SUFFIXES:
+        path = os.path.join(PKG_DIR, "_hiphealth" + suffix)
+        if os.path.exists(path):
+            return path
+    return ""
+
+
+# ---------------------------------------------------------------------------
+# result
+# ---------------------------------------------------------------------------
+@dataclass
+class SelftestResult:
+    gpu_index: int
+    bdf: str
+    #: pass | memory | compute | error
+    outcome: str
+    #: the child's JSON object (None when there is none to trust)
+    report: Optional[dict] = None
+    error: str = ""
+    seconds: float = 0.0
+
+    def findings(self) -> list:
+        """The result as health findings: none for a pass."""
+        from .plugin.health import REASONS, HealthFinding
+
+        severity = dict(REASONS)
+
+        def finding(reason, detail):
+            return HealthFinding(reason, severity[reason], detail)
+
+        if self.outcome == "pass":
+            return []
+        if self.outcome == "error":
+            return [finding("SelftestError", self.error)]
+        out = []
+        report = self.report or {}
+        for p in report.get("memory", ()):
+            if not p["mismatches"]:
+                continue
+            detail = f"pattern {p['pattern']}: {p['mismatches']} mismatching word(s)"
+            if p["records"]:
+                word, got, want = min(p["records"])
+                detail += (
+                    f"; first recorded word {word}: got 0x{got:016x}, "
+                    f"want 0x{want:016x}"
+                )
+            out.append(finding("SelftestMemoryMismatch", detail))
+        mfma = report.get("mfma") or {}
+        if mfma.get("mismatches"):
+            detail = f"{mfma['mismatches']} mismatching accumulator value(s)"
+            if mfma["records"]:
+                wave, lane, slot, got, want = min(mfma["records"])
+                detail += (
+                    f"; first recorded wave {wave} lane {lane} slot {slot}: "
+                    f"got 0x{got:08x}, want 0x{want:08x}"
+                )
+            out.append(finding("SelftestComputeMismatch", detail))
+        return out
+
+
+def _classify(report: dict) -> str:
+    """pass | memory | compute from a child's report; raises on a report
+    that does not have the documented shape."""
+    memory_bad = any(int(p["mismatches"]) for p in report["memory"])
+    compute_bad = bool(int(report["mfma"]["mismatches"]))
+    for part in list(report["memory"]) + [report["mfma"]]:
+        part["records"] = [tuple(int(v) for v in r) for r in part["records"]]
+    if any("pattern" not in p for p in report["memory"]):
+        raise KeyError("pattern")
+    if memory_bad:
+        return "memory"
+    if compute_bad:
+        return "compute"
+    if not report["ok"]:
+        raise ValueError("report says not ok but lists no mismatch")
+    return "pass"
+
+
+# ---------------------------------------------------------------------------
+# parent
+# ---------------------------------------------------------------------------
+def _spawn_child(argv: List[str], timeout_s: float) -> Tuple[int, str, str]:
+    env = dict(os.environ)
+    # the child must import this very package
+    root = os.path.dirname(PKG_DIR)
+    env["PYTHONPATH"] = os.pathsep.join(
+        p for p in (root, env.get("PYTHONPATH", "")) if p
+    )
+    # subprocess.run kills the child and reaps it when the timeout expires
+    done = subprocess.run(
+        argv,
+        capture_output=True,
+        text=True,
+        env=env,
+        timeout=timeout_s,
+        stdin=subprocess.DEVNULL,
+    )
+    return done.returncode, done.stdout, done.stderr
+
+
+#: one child at a time, whoever calls
+_one_child = threading.Lock()
+
+
+def run(
+    gpu,
+    *,
+    mib: int = DEFAULT_MIB,
+    timeout_s: float = DEFAULT_TIMEOUT_S,
+    spawn: Spawn = _spawn_child,
+) -> SelftestResult:
+    """Self-test one GPU (a ``hal.model.GpuInfo``: ``index`` and
+    ``pcie_bdf`` are used) in a child process. Never raises and never
+    retries: whatever goes wrong is an ``error`` result."""
+    bdf = gpu.pcie_bdf
+    argv = [
+        sys.executable,
+        "-m",
+        "k8s_dra_driver_amd.selftest",
+        "--bdf",
+        bdf,
+        "--mib",
+        str(int(mib)),
+        "--json",
+    ]
+
+    def result(outcome, report=None, error=""):
+        return SelftestResult(
+            gpu_index=gpu.index,
+            bdf=bdf,
+            outcome=outcome,
+            report=report,
+            error=error,
+            seconds=time.monotonic() - t0,
+        )
+
+    with _one_child:
+        t0 = time.monotonic()
+        try:
+            rc, out, err = spawn(argv, timeout_s)
+        except subprocess.TimeoutExpired:
+            return result("error", error=f"timed out after {timeout_s:g}s; child killed")
+        except Exception as e:
+            return result("error", error=f"could not start the self-test: {e}")
+        last = (out.strip().splitlines() or [""])[-1]
+        try:
+            report = json.loads(last)
+            if not isinstance(report, dict):
+                raise ValueError("not a JSON object")
+        except ValueError:
+            tail = (err.strip().splitlines() or [""])[-1]
+            return result(
+                "error",
+                error=f"exit {rc}, unparsable output {last[:80]!r}"
+                + (f" ({tail[:200]})" if tail else ""),
+            )
+        if rc == EXIT_ERROR or rc not in (EXIT_PASS, EXIT_MISMATCH):
+            return result(
+                "error",
+                report=report,
+                error=f"exit {rc}: {report.get('error', 'no reason given')}",
+            )
+        try:
+            outcome = _classify(report)
+        except (KeyError, TypeError, ValueError) as e:
+            return result("error", error=f"exit {rc}, malformed report: {e!r}")
+        if (outcome == "pass") != (rc == EXIT_PASS):
+            return result(
+                "error", error=f"exit {rc} contradicts the report ({outcome})"
+            )
+        return result(outcome, report=report)
+
+
+# ---------------------------------------------------------------------------
+# child
+# ---------------------------------------------------------------------------
+def _child(bdf: str, mib: int) -> Tuple[int, dict]:
+    try:
+        from k8s_dra_driver_amd import _hiphealth
+
+        want = bdf.strip().lower()
+        seen = []
+        for ordinal in range(_hiphealth.device_count()):
+            have = _hiphealth.pci_bus_id(ordinal).strip().lower()
+            seen.append(have)
+            if have == want:
+                report = _hiphealth.selftest(ordinal, mib=mib)
+                report["bdf"] = have
+                return (EXIT_PASS if report["ok"] else EXIT_MISMATCH), report
+        return EXIT_ERROR, {
+            "ok": False,
+            "error": f"no HIP device at {bdf} (visible: {seen or 'none'})",
+        }
+    except Exception as e:
+        return EXIT_ERROR, {"ok": False, "error": f"{type(e).__name__}: {e}"}
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(
+        "python -m k8s_dra_driver_amd.selftest",
+        description="self-test one GPU; exit 0 passed, 1 mismatches, 2 could not run",
+    )
+    ap.add_argument("--bdf", required=True, help="PCI address, e.g. 0000:c1:00.0")
+    ap.add_argument("--mib", type=int, default=DEFAULT_MIB, help="HBM region to test")
+    ap.add_argument("--json", action="store_true", help="print the full report")
+    args = ap.parse_args(argv)
+    t0 = time.monotonic()
+    rc, report = _child(args.bdf, args.mib)
+    report["seconds"] = round(time.monotonic() - t0, 3)
+    if args.json:
+        print(json.dumps(report, sort_keys=True))
+    elif "error" in report:
+        print(f"{args.bdf}: error: {report['error']}")
+    else:
+        bad = sum(p["mismatches"] for p in report["memory"])
+        print(
+            f"{args.bdf}: {'ok' if report['ok'] else 'FAILED'}: "
+            f"{report['bytes'] >> 20} MiB x 4 patterns, {bad} memory "
+            f"mismatch(es); mfma {report['mfma']['mismatches']} mismatch(es) "
+            f"in {report['mfma']['checked']} values"
+        )
+    return rc
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -111,6 +111,17 @@ def main(argv=None) -> int:
         default=0,
         help="RCCL all-reduce of this buffer size across visible GPUs",
     )
+    ap.add_argument(
+        "--selftest",
+        type=int,
+        nargs="?",
+        const=1024,
+        default=0,
+        metavar="MiB",
+        help="fill and verify this much HBM (default 1024 MiB) with known "
+        "patterns and run the MFMA known-answer test on every visible "
+        "device; exit 1 on a mismatch",
+    )
     args = ap.parse_args(argv)
 
     info = visible_devices()
@@ -118,7 +129,8 @@ def main(argv=None) -> int:
     if not info["kfd"] or not info["render_nodes"]:
         print("ERROR: no GPU devices injected", file=sys.stderr)
         return 1
-    if args.benchmark or args.burn_ms or args.nbody:
+    rc = 0
+    if args.benchmark or args.burn_ms or args.nbody or args.selftest:
         from k8s_dra_driver_amd import _hiphealth
 
         n = _hiphealth.device_count()
@@ -137,9 +149,20 @@ def main(argv=None) -> int:
                     f"device {d}: nbody {r['bodies']} bodies x {r['iters']} "
                     f"iters = {r['gflops']:.0f} GFLOP/s finite={r['finite']}"
                 )
+            if args.selftest:
+                r = _hiphealth.selftest(d, mib=args.selftest)
+                bad = sum(p["mismatches"] for p in r["memory"])
+                print(
+                    f"device {d}: selftest {'ok' if r['ok'] else 'FAILED'}: "
+                    f"{args.selftest} MiB x 4 patterns, {bad} memory "
+                    f"mismatch(es), mfma {r['mfma']['mismatches']} "
+                    f"mismatch(es) in {r['mfma']['checked']} values"
+                )
+                if not r["ok"]:
+                    rc = 1
     if args.allreduce_mb:
-        return run_allreduce(args.allreduce_mb)
-    return 0
+        return run_allreduce(args.allreduce_mb) or rc
+    return rc
 
 
 if __name__ == "__main__":
