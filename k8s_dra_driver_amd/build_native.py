@@ -98,12 +98,15 @@ def build_amdhal_asan(force: bool = False) -> str:
 
 
 def build_hiphealth(force: bool = False) -> str:
-    """HIP kernels; rebuilt when the source or the self-test header it
-    includes changes."""
+    """HIP kernels; rebuilt when the source or a header it includes (the
+    self-test's, the CU footprint's) changes."""
     src = os.path.join(CPP_DIR, "hiphealth.hip")
-    hdr = os.path.join(CPP_DIR, "selftest_kernels.hpp")
+    hdrs = [
+        os.path.join(CPP_DIR, "selftest_kernels.hpp"),
+        os.path.join(CPP_DIR, "footprint_kernels.hpp"),
+    ]
     out = os.path.join(PKG_DIR, f"_hiphealth{_ext_suffix()}")
-    if force or _needs_build(src, out) or _needs_build(hdr, out):
+    if force or _needs_build(src, out) or any(_needs_build(h, out) for h in hdrs):
         hipcc = os.path.join(ROCM, "bin", "hipcc")
         if not os.path.exists(hipcc):
             hipcc = "hipcc"

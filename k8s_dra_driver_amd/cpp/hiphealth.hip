@@ -16,6 +16,9 @@
 //   selftest()       - startup self-test: HBM fill/verify with four
 //                      patterns and an MFMA known-answer test
 //                      (selftest_kernels.hpp)
+//   cu_footprint()   - the distinct compute units the blocks of one launch
+//                      ran on, read from the hardware id registers
+//                      (footprint_kernels.hpp)
 //
 // Written for gfx950: 64-wide waves, 256 CUs in 8 XCDs (grids sized
 // >> 256 workgroups), 16 B/lane streaming accesses.
@@ -647,6 +650,11 @@ py::bytes mfma_burn_probe(int device, int iters, int blocks) {
 #include "selftest_kernels.hpp"
 
 // ---------------------------------------------------------------------------
+// CU footprint: which compute units this process's blocks run on
+// ---------------------------------------------------------------------------
+#include "footprint_kernels.hpp"
+
+// ---------------------------------------------------------------------------
 // device info
 // ---------------------------------------------------------------------------
 int device_count() {
@@ -739,4 +747,20 @@ PYBIND11_MODULE(_hiphealth, m) {
         "compared)");
   m.def("pci_bus_id", &pci_bus_id, py::arg("device") = 0,
         "PCI address (domain:bus:device.function) of a HIP device");
+  m.attr("FOOTPRINT_DEFAULT_SPIN") = kFootDefaultSpin;
+  m.attr("FOOTPRINT_MAX_SPIN") = kFootMaxSpin;
+  m.attr("FOOTPRINT_MAX_BLOCKS") = kProbeMaxBlocks;
+  m.def("cu_footprint", &cu_footprint, py::arg("device") = 0,
+        py::arg("blocks") = 0, py::arg("spin") = 0,
+        "One launch of cu_where with grid=blocks (0 = 8 per CU, at most "
+        "4096), block=1024 and spin dependent FMAs per thread (0 = "
+        "FOOTPRINT_DEFAULT_SPIN). Returns {cus: sorted distinct (xcc, se, "
+        "sh, cu), count, per_xcc: {xcc: CUs}, blocks_per_cu_min, "
+        "blocks_per_cu_max, blocks, spin, multi_processor_count, "
+        "kernel_ms}; kernel_ms is event-timed and informative only");
+  m.def("cu_footprint_probe", &cu_footprint_probe, py::arg("device"),
+        py::arg("blocks"), py::arg("spin"),
+        "One launch of cu_where with grid=blocks, block=1024 and exactly "
+        "spin FMAs per thread; returns guard + blocks x (hw_id, xcc_id, "
+        "block, 0) uint32 + guard, the register words undecoded");
 }

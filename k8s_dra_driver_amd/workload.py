@@ -93,6 +93,52 @@ def run_allreduce(size_mb: int) -> int:
     return 0 if all(ok for _, ok in per_gpu.values()) else 1
 
 
+def cu_footprint_rows(counts: dict, cu_mask: str) -> list:
+    """One row per device for ``--cu-footprint``: ``(device, CUs seen, bits
+    of this process's HSA_CU_MASK entry for that ordinal or None)``.
+    ``counts`` is ``{device: CUs seen}``; an unparsable mask raises
+    ``ValueError``."""
+    from .sharing.footprint import parse_cu_mask, popcount
+
+    masks = parse_cu_mask(cu_mask) if cu_mask else {}
+    return [
+        (d, counts[d], popcount(masks[d]) if d in masks else None)
+        for d in sorted(counts)
+    ]
+
+
+def cu_footprint_exit_code(rows) -> int:
+    """The verdict of ``--cu-footprint``: 1 when any device shows more CUs
+    than its mask has bits, else 0. A device with no mask entry is allowed
+    everything."""
+    return int(any(bits is not None and seen > bits for _, seen, bits in rows))
+
+
+def run_cu_footprint(hh) -> int:
+    """Print, for every visible device, where this process's blocks run;
+    exit code as :func:`cu_footprint_exit_code`."""
+    cu_mask = os.environ.get("HSA_CU_MASK", "")
+    reports = {d: hh.cu_footprint(d) for d in range(hh.device_count())}
+    if not reports:
+        print("ERROR: no HIP devices to measure", file=sys.stderr)
+        return 1
+    try:
+        rows = cu_footprint_rows({d: r["count"] for d, r in reports.items()}, cu_mask)
+    except ValueError as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        return 1
+    for d, seen, bits in rows:
+        r = reports[d]
+        per_xcd = " ".join(f"{x}:{n}" for x, n in sorted(r["per_xcc"].items()))
+        allowed = "no mask" if bits is None else f"mask allows {bits}"
+        verdict = "EXCEEDS MASK" if bits is not None and seen > bits else "ok"
+        print(
+            f"device {d}: cu footprint {seen} of {r['multi_processor_count']} "
+            f"CUs, per XCD {per_xcd}; {allowed}: {verdict}"
+        )
+    return cu_footprint_exit_code(rows)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser("amd-dra-workload")
     ap.add_argument("--list", action="store_true", help="print visible devices (nvidia-smi -L analog)")
@@ -122,6 +168,13 @@ def main(argv=None) -> int:
         "patterns and run the MFMA known-answer test on every visible "
         "device; exit 1 on a mismatch",
     )
+    ap.add_argument(
+        "--cu-footprint",
+        action="store_true",
+        help="print which compute units this process's blocks run on, per "
+        "device and per XCD, next to the size of its HSA_CU_MASK entry; "
+        "exit 1 if a device shows more CUs than its mask allows",
+    )
     args = ap.parse_args(argv)
 
     info = visible_devices()
@@ -130,11 +183,13 @@ def main(argv=None) -> int:
         print("ERROR: no GPU devices injected", file=sys.stderr)
         return 1
     rc = 0
-    if args.benchmark or args.burn_ms or args.nbody or args.selftest:
+    if args.benchmark or args.burn_ms or args.nbody or args.selftest or args.cu_footprint:
         from k8s_dra_driver_amd import _hiphealth
 
         n = _hiphealth.device_count()
         print(f"hip devices: {n}")
+        if args.cu_footprint:
+            rc = run_cu_footprint(_hiphealth) or rc
         for d in range(n):
             if args.benchmark:
                 bw = _hiphealth.bandwidth_gbs(d, 256, 5)
