@@ -99,11 +99,12 @@ def build_amdhal_asan(force: bool = False) -> str:
 
 def build_hiphealth(force: bool = False) -> str:
     """HIP kernels; rebuilt when the source or a header it includes (the
-    self-test's, the CU footprint's) changes."""
+    self-test's, the CU footprint's, the per-CU self-test's) changes."""
     src = os.path.join(CPP_DIR, "hiphealth.hip")
     hdrs = [
         os.path.join(CPP_DIR, "selftest_kernels.hpp"),
         os.path.join(CPP_DIR, "footprint_kernels.hpp"),
+        os.path.join(CPP_DIR, "cutest_kernels.hpp"),
     ]
     out = os.path.join(PKG_DIR, f"_hiphealth{_ext_suffix()}")
     if force or _needs_build(src, out) or any(_needs_build(h, out) for h in hdrs):

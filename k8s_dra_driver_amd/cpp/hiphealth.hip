@@ -19,6 +19,9 @@
 //   cu_footprint()   - the distinct compute units the blocks of one launch
 //                      ran on, read from the hardware id registers
 //                      (footprint_kernels.hpp)
+//   cu_selftest()    - per-CU self-test: an LDS pattern test and the MFMA
+//                      known-answer table on every CU, mismatches named by
+//                      (xcc, se, sh, cu) (cutest_kernels.hpp)
 //
 // Written for gfx950: 64-wide waves, 256 CUs in 8 XCDs (grids sized
 // >> 256 workgroups), 16 B/lane streaming accesses.
@@ -655,6 +658,11 @@ py::bytes mfma_burn_probe(int device, int iters, int blocks) {
 #include "footprint_kernels.hpp"
 
 // ---------------------------------------------------------------------------
+// per-CU self-test: LDS pattern test + MFMA known answers, named by CU
+// ---------------------------------------------------------------------------
+#include "cutest_kernels.hpp"
+
+// ---------------------------------------------------------------------------
 // device info
 // ---------------------------------------------------------------------------
 int device_count() {
@@ -763,4 +771,30 @@ PYBIND11_MODULE(_hiphealth, m) {
         "One launch of cu_where with grid=blocks, block=1024 and exactly "
         "spin FMAs per thread; returns guard + blocks x (hw_id, xcc_id, "
         "block, 0) uint32 + guard, the register words undecoded");
+  m.attr("CUTEST_LDS_BYTES") = kCuLdsBytes;
+  m.attr("CUTEST_BLOCKS_PER_CU") = kCuBlocksPerCu;
+  m.def("cu_selftest", &cu_selftest, py::arg("device") = 0,
+        py::arg("seed") = 0x5E1F7E57C0FFEEull, py::arg("blocks") = 0,
+        "One launch of cu_test with grid=blocks (0 = CUTEST_BLOCKS_PER_CU "
+        "per CU, at most 4096), block=256, over all CUTEST_LDS_BYTES of LDS: "
+        "every block fills and verifies its CU's LDS with addr, addr_inv, "
+        "hash and hash_inv, runs all 16 known-answer vectors on each of its "
+        "four waves and records where it ran. Returns {ok, device, seed, "
+        "blocks, lds_bytes, multi_processor_count, covered, per_xcc: {xcc: "
+        "CUs}, blocks_per_cu_min, blocks_per_cu_max, simds_per_cu_min, lds: "
+        "{checked_words, mismatches, records: [(block, pattern, word, got, "
+        "want)]}, mfma: {checked, mismatches, records: [(block, wave, "
+        "vector, lane, slot, got_bits, want_bits)]}, bad_cus: [{xcc, se, sh, "
+        "cu, blocks, lds_mismatches, mfma_mismatches}], kernel_ms}; coverage "
+        "is reported, not judged, and kernel_ms is informative only");
+  m.def("cu_selftest_probe", &cu_selftest_probe, py::arg("device"),
+        py::arg("a_tab"), py::arg("b_tab"), py::arg("c_tab"),
+        py::arg("want_tab"), py::arg("seed"), py::arg("blocks"),
+        py::arg("lds_bytes"), py::arg("flips"),
+        "cu_test on the caller's 16-vector table over the first lds_bytes "
+        "of LDS with grid=blocks; every (block, pattern, word, mask) of "
+        "flips is XORed into that block's LDS while it holds that pattern. "
+        "Returns (guard + blocks x (hw_id, xcc_id, block, simd_mask, "
+        "lds_mismatches, mfma_mismatches, 0, 0) uint32 + guard, the dict of "
+        "cu_selftest)");
 }

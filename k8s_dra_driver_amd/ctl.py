@@ -11,6 +11,7 @@ projection, carve/restore partitions, and run the health probes.
     amd-dra-ctl health               # per-GPU health + HIP probes
     amd-dra-ctl health --signals     # + ECC / retired-page / thermal signals
     amd-dra-ctl health --selftest    # + HBM pattern / MFMA known-answer test
+    amd-dra-ctl health --selftest --per-cu   # + LDS / MFMA test of every CU
 Use ``--hal fake`` anywhere to drive the modeled 8xMI355X node.
 """
 
@@ -190,7 +191,7 @@ def _print_signals(rec: dict) -> None:
         print(f"    unsupported {k}: {why}")
 
 
-def _selftest_into(rec: dict, g, mib: int) -> None:
+def _selftest_into(rec: dict, g, mib: int, per_cu: bool = False) -> None:
     """Self-test one GPU in a child process and add what it found to the
     GPU's record. The operator vouches that nothing is using the GPU; a
     partitioned GPU, or one without a PCI address, is skipped."""
@@ -199,12 +200,19 @@ def _selftest_into(rec: dict, g, mib: int) -> None:
     if g.compute_partition.upper() != "SPX" or g.partitions or not g.pcie_bdf:
         rec["selftest"] = {"result": "skipped"}
         return
-    res = selftest.run(g, mib=mib)
+    res = selftest.run(g, mib=mib, **({"per_cu": True} if per_cu else {}))
     rec["selftest"] = {
         "result": res.outcome,
         "seconds": round(res.seconds, 3),
         "mib": mib,
     }
+    cu = (res.report or {}).get("cu") if per_cu else None
+    if cu:
+        rec["selftest"]["cu"] = {
+            "covered": cu["covered"],
+            "expected": cu["multi_processor_count"],
+            "bad_cus": cu["bad_cus"],
+        }
     rec["findings"] += [
         {"reason": f.reason, "severity": f.severity, "detail": f.detail}
         for f in res.findings()
@@ -218,7 +226,7 @@ def cmd_health(args) -> int:
     for g in lib.enumerate():
         rec = _health_record(lib, g)
         if args.selftest:
-            _selftest_into(rec, g, args.selftest_mib)
+            _selftest_into(rec, g, args.selftest_mib, args.per_cu)
         records.append(rec)
         if not args.json:
             print(f"{g.canonical_name}: {rec['health']}")
@@ -230,6 +238,18 @@ def cmd_health(args) -> int:
                     f"    selftest: {st['result']}"
                     + (f" ({st['seconds']:.1f}s)" if "seconds" in st else "")
                 )
+                if "cu" in st:
+                    cu = st["cu"]
+                    print(
+                        f"    per CU: {cu['covered']} of {cu['expected']} CUs "
+                        f"covered, {len(cu['bad_cus'])} bad"
+                    )
+                    for c in cu["bad_cus"]:
+                        print(
+                            f"      xcc {c['xcc']} se {c['se']} sh {c['sh']} "
+                            f"cu {c['cu']}: lds {c['lds_mismatches']}, "
+                            f"mfma {c['mfma_mismatches']}"
+                        )
                 if not args.signals:
                     for f in rec["findings"]:
                         if f["reason"].startswith("Selftest"):
@@ -324,6 +344,12 @@ def main(argv=None) -> int:
         help="also fill and verify HBM with known patterns and run the MFMA "
         "known-answer test, one GPU at a time in a child process; only for "
         "GPUs that nothing is using",
+    )
+    hp.add_argument(
+        "--per-cu",
+        action="store_true",
+        help="with --selftest, also test the LDS and the matrix pipes of "
+        "every compute unit and name the CUs that fail",
     )
     hp.add_argument(
         "--selftest-mib",

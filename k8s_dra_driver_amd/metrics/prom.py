@@ -139,6 +139,20 @@ class PluginMetrics:
             ["gpu"],
             registry=self.registry,
         )
+        # its per-CU stage, set only when that stage ran
+        self.gpu_selftest_cus_covered = Gauge(
+            "dra_gpu_selftest_cus_covered",
+            "Compute units the last per-CU startup self-test ran on",
+            ["gpu"],
+            registry=self.registry,
+        )
+        self.gpu_selftest_cus_bad = Gauge(
+            "dra_gpu_selftest_cus_bad",
+            "Compute units with an LDS or MFMA mismatch in the last per-CU "
+            "startup self-test",
+            ["gpu"],
+            registry=self.registry,
+        )
         #: gpu label -> reason label currently exported as dra_gpu_unhealthy
         self._unhealthy_reason = {}
 

@@ -221,7 +221,12 @@ class Driver:
 
     # ------------------------------------------------------------------
     def run_startup_selftest(
-        self, runner=None, *, mib: int = 1024, timeout_s: float = 120.0
+        self,
+        runner=None,
+        *,
+        mib: int = 1024,
+        timeout_s: float = 120.0,
+        per_cu: bool = False,
     ) -> Dict[int, str]:
         """Self-test every GPU in scope that nothing is using, one after
         another, and hand the findings to the health monitor. Meant for
@@ -229,6 +234,8 @@ class Driver:
         slice is published and no gRPC server exists, so nothing can start
         using a GPU while it is tested. Returns ``{gpu index: result}``
         with result in pass | memory | compute | error | skipped.
+        ``per_cu`` adds the per-CU stage (LDS and matrix pipes of every
+        compute unit); only then is the runner called with ``per_cu=True``.
 
         A GPU is skipped (logged, no finding) when a claim recovered from
         the checkpoints holds it, when it is partitioned, or when it has
@@ -257,9 +264,13 @@ class Driver:
                 self.metrics.gpu_selftest_runs.labels(str(idx), "skipped").inc()
                 continue
             t0 = time.perf_counter()
+            extra = {"per_cu": True} if per_cu else {}
+            cu = None
             try:
-                res = runner(gpu, mib=mib, timeout_s=timeout_s)
+                res = runner(gpu, mib=mib, timeout_s=timeout_s, **extra)
                 outcome, findings = res.outcome, res.findings()
+                if per_cu:
+                    cu = (res.report or {}).get("cu")
             except Exception as e:
                 log.exception("gpu-%d: startup self-test failed to run", idx)
                 from .health import HealthFinding, SOFT
@@ -270,6 +281,13 @@ class Driver:
             results[idx] = outcome
             self.metrics.gpu_selftest_runs.labels(str(idx), outcome).inc()
             self.metrics.gpu_selftest_seconds.labels(str(idx)).set(seconds)
+            if cu:
+                self.metrics.gpu_selftest_cus_covered.labels(str(idx)).set(
+                    cu["covered"]
+                )
+                self.metrics.gpu_selftest_cus_bad.labels(str(idx)).set(
+                    len(cu["bad_cus"])
+                )
             self.health.set_selftest_findings(idx, findings)
             if findings:
                 for f in findings:
@@ -278,7 +296,13 @@ class Driver:
                     )
             else:
                 log.info(
-                    "gpu-%d: startup self-test passed in %.1fs", idx, seconds
+                    "gpu-%d: startup self-test passed in %.1fs%s",
+                    idx,
+                    seconds,
+                    f"; {cu['covered']} of {cu['multi_processor_count']} "
+                    "CUs covered"
+                    if cu
+                    else "",
                 )
         self.health.check_once()
         return results

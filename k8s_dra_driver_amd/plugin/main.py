@@ -147,6 +147,13 @@ def build_parser() -> argparse.ArgumentParser:
         "below 256 the region may never leave the Infinity Cache)",
     )
     p.add_argument(
+        "--selftest-per-cu",
+        default=_env("SELFTEST_PER_CU", "off"),
+        choices=["off", "on"],
+        help="with --startup-selftest on, also test the LDS and the matrix "
+        "pipes of every compute unit and name the CUs that fail",
+    )
+    p.add_argument(
         "--selftest-timeout-s",
         type=float,
         default=float(_env("SELFTEST_TIMEOUT_S", "120")),
@@ -197,8 +204,9 @@ def startup_selftest(args, driver) -> bool:
     slice already carries the taint of a GPU that failed."""
     if args.startup_selftest != "on":
         return False
+    extra = {"per_cu": True} if args.selftest_per_cu == "on" else {}
     driver.run_startup_selftest(
-        mib=args.selftest_mib, timeout_s=args.selftest_timeout_s
+        mib=args.selftest_mib, timeout_s=args.selftest_timeout_s, **extra
     )
     return True
 

@@ -13,7 +13,10 @@ Two halves:
   --json``): finds the HIP device with that PCI address, runs
   ``_hiphealth.selftest`` on it and prints one JSON object. Exit 0 = passed,
   1 = mismatches found, 2 = could not run. Imports neither torch nor the
-  plugin.
+  plugin. With ``--per-cu`` it goes on to ``_hiphealth.cu_selftest`` (LDS
+  pattern test and the whole known-answer table on every compute unit) and
+  puts that result under ``"cu"``: a mismatch then carries the name of the
+  CU it happened on.
 - **parent** (:func:`run`): starts that child in a fresh process with a
   timeout, one child at a time, and turns what it says into a
   :class:`SelftestResult`. The calling process never initialises HIP, so a
@@ -108,7 +111,66 @@ class SelftestResult:
                     f"got 0x{got:08x}, want 0x{want:08x}"
                 )
             out.append(finding("SelftestComputeMismatch", detail))
+        cu = report.get("cu") or {}
+        if cu.get("bad_cus"):
+            out.append(finding("SelftestComputeMismatch", _cu_detail(cu)))
         return out
+
+
+#: how many bad CUs a finding spells out
+MAX_CUS_IN_DETAIL = 4
+
+
+def _cu_detail(cu: dict) -> str:
+    """The per-CU part of a report as one finding's text: how many CUs are
+    bad out of those covered, the first few by name, and the lowest record
+    of each kind."""
+    bad = cu["bad_cus"]
+    detail = f"per-CU test: {len(bad)} of {cu['covered']} covered CU(s) bad: "
+    detail += ", ".join(
+        f"xcc {c['xcc']} se {c['se']} sh {c['sh']} cu {c['cu']} "
+        f"(lds {c['lds_mismatches']}, mfma {c['mfma_mismatches']})"
+        for c in bad[:MAX_CUS_IN_DETAIL]
+    )
+    if len(bad) > MAX_CUS_IN_DETAIL:
+        detail += f", and {len(bad) - MAX_CUS_IN_DETAIL} more"
+    if cu["lds"]["records"]:
+        block, pattern, word, got, want = min(cu["lds"]["records"])
+        detail += (
+            f"; first recorded LDS word: block {block} pattern {pattern} "
+            f"word {word}: got 0x{got:016x}, want 0x{want:016x}"
+        )
+    if cu["mfma"]["records"]:
+        block, wave, vector, lane, slot, got, want = min(cu["mfma"]["records"])
+        detail += (
+            f"; first recorded MFMA value: block {block} wave {wave} vector "
+            f"{vector} lane {lane} slot {slot}: got 0x{got:08x}, "
+            f"want 0x{want:08x}"
+        )
+    return detail
+
+
+def _classify_cu(cu) -> bool:
+    """True when the per-CU part of a report lists a mismatch; raises on a
+    part that does not have the documented shape."""
+    if not isinstance(cu, dict):
+        raise TypeError("cu is not an object")
+    lds, mfma = cu["lds"], cu["mfma"]
+    bad = bool(int(lds["mismatches"])) or bool(int(mfma["mismatches"]))
+    lds["records"] = [
+        (int(b), str(p), int(w), int(got), int(want))
+        for b, p, w, got, want in lds["records"]
+    ]
+    mfma["records"] = [tuple(int(v) for v in r) for r in mfma["records"]]
+    if any(len(r) != 7 for r in mfma["records"]):
+        raise ValueError("an MFMA record of cu does not have 7 fields")
+    cu["covered"] = int(cu["covered"])
+    cu["multi_processor_count"] = int(cu["multi_processor_count"])
+    names = ("xcc", "se", "sh", "cu", "blocks", "lds_mismatches", "mfma_mismatches")
+    cu["bad_cus"] = [{k: int(c[k]) for k in names} for c in cu["bad_cus"]]
+    if bad != bool(cu["bad_cus"]) or bad == bool(cu["ok"]):
+        raise ValueError("cu: ok, the mismatch counts and bad_cus disagree")
+    return bad
 
 
 def _classify(report: dict) -> str:
@@ -116,6 +178,8 @@ def _classify(report: dict) -> str:
     that does not have the documented shape."""
     memory_bad = any(int(p["mismatches"]) for p in report["memory"])
     compute_bad = bool(int(report["mfma"]["mismatches"]))
+    if "cu" in report and _classify_cu(report["cu"]):
+        compute_bad = True
     for part in list(report["memory"]) + [report["mfma"]]:
         part["records"] = [tuple(int(v) for v in r) for r in part["records"]]
     if any("pattern" not in p for p in report["memory"]):
@@ -161,10 +225,12 @@ def run(
     mib: int = DEFAULT_MIB,
     timeout_s: float = DEFAULT_TIMEOUT_S,
     spawn: Spawn = _spawn_child,
+    per_cu: bool = False,
 ) -> SelftestResult:
     """Self-test one GPU (a ``hal.model.GpuInfo``: ``index`` and
-    ``pcie_bdf`` are used) in a child process. Never raises and never
-    retries: whatever goes wrong is an ``error`` result."""
+    ``pcie_bdf`` are used) in a child process; ``per_cu`` adds the per-CU
+    stage. Never raises and never retries: whatever goes wrong is an
+    ``error`` result."""
     bdf = gpu.pcie_bdf
     argv = [
         sys.executable,
@@ -176,6 +242,8 @@ def run(
         str(int(mib)),
         "--json",
     ]
+    if per_cu:
+        argv.append("--per-cu")
 
     def result(outcome, report=None, error=""):
         return SelftestResult(
@@ -214,6 +282,8 @@ def run(
                 error=f"exit {rc}: {report.get('error', 'no reason given')}",
             )
         try:
+            if per_cu and "cu" not in report:
+                raise KeyError("cu")
             outcome = _classify(report)
         except (KeyError, TypeError, ValueError) as e:
             return result("error", error=f"exit {rc}, malformed report: {e!r}")
@@ -227,7 +297,7 @@ def run(
 # ---------------------------------------------------------------------------
 # child
 # ---------------------------------------------------------------------------
-def _child(bdf: str, mib: int) -> Tuple[int, dict]:
+def _child(bdf: str, mib: int, per_cu: bool = False) -> Tuple[int, dict]:
     try:
         from k8s_dra_driver_amd import _hiphealth
 
@@ -239,6 +309,9 @@ def _child(bdf: str, mib: int) -> Tuple[int, dict]:
             if have == want:
                 report = _hiphealth.selftest(ordinal, mib=mib)
                 report["bdf"] = have
+                if per_cu:
+                    report["cu"] = _hiphealth.cu_selftest(ordinal)
+                    report["ok"] = bool(report["ok"] and report["cu"]["ok"])
                 return (EXIT_PASS if report["ok"] else EXIT_MISMATCH), report
         return EXIT_ERROR, {
             "ok": False,
@@ -255,10 +328,15 @@ def main(argv=None) -> int:
     )
     ap.add_argument("--bdf", required=True, help="PCI address, e.g. 0000:c1:00.0")
     ap.add_argument("--mib", type=int, default=DEFAULT_MIB, help="HBM region to test")
+    ap.add_argument(
+        "--per-cu",
+        action="store_true",
+        help="also test every compute unit's LDS and matrix pipes, by name",
+    )
     ap.add_argument("--json", action="store_true", help="print the full report")
     args = ap.parse_args(argv)
     t0 = time.monotonic()
-    rc, report = _child(args.bdf, args.mib)
+    rc, report = _child(args.bdf, args.mib, args.per_cu)
     report["seconds"] = round(time.monotonic() - t0, 3)
     if args.json:
         print(json.dumps(report, sort_keys=True))
@@ -272,6 +350,14 @@ def main(argv=None) -> int:
             f"mismatch(es); mfma {report['mfma']['mismatches']} mismatch(es) "
             f"in {report['mfma']['checked']} values"
         )
+        if "cu" in report:
+            cu = report["cu"]
+            print(
+                f"{args.bdf}: per CU: {cu['covered']} of "
+                f"{cu['multi_processor_count']} CUs covered, "
+                f"{len(cu['bad_cus'])} bad; lds {cu['lds']['mismatches']} "
+                f"mismatch(es), mfma {cu['mfma']['mismatches']} mismatch(es)"
+            )
     return rc
 
 

@@ -169,6 +169,13 @@ def main(argv=None) -> int:
         "device; exit 1 on a mismatch",
     )
     ap.add_argument(
+        "--cu-selftest",
+        action="store_true",
+        help="test the LDS and the matrix pipes of every compute unit of "
+        "every visible device and name the CUs that fail; exit 1 on a "
+        "mismatch",
+    )
+    ap.add_argument(
         "--cu-footprint",
         action="store_true",
         help="print which compute units this process's blocks run on, per "
@@ -183,7 +190,14 @@ def main(argv=None) -> int:
         print("ERROR: no GPU devices injected", file=sys.stderr)
         return 1
     rc = 0
-    if args.benchmark or args.burn_ms or args.nbody or args.selftest or args.cu_footprint:
+    if (
+        args.benchmark
+        or args.burn_ms
+        or args.nbody
+        or args.selftest
+        or args.cu_selftest
+        or args.cu_footprint
+    ):
         from k8s_dra_driver_amd import _hiphealth
 
         n = _hiphealth.device_count()
@@ -212,6 +226,22 @@ def main(argv=None) -> int:
                     f"{args.selftest} MiB x 4 patterns, {bad} memory "
                     f"mismatch(es), mfma {r['mfma']['mismatches']} "
                     f"mismatch(es) in {r['mfma']['checked']} values"
+                )
+                if not r["ok"]:
+                    rc = 1
+            if args.cu_selftest:
+                r = _hiphealth.cu_selftest(d)
+                bad = ", ".join(
+                    f"xcc {c['xcc']} se {c['se']} sh {c['sh']} cu {c['cu']}"
+                    for c in r["bad_cus"]
+                )
+                print(
+                    f"device {d}: cu-selftest {'ok' if r['ok'] else 'FAILED'}: "
+                    f"{r['covered']} of {r['multi_processor_count']} CUs "
+                    f"covered by {r['blocks']} blocks, lds "
+                    f"{r['lds']['mismatches']} mismatch(es), mfma "
+                    f"{r['mfma']['mismatches']} mismatch(es), "
+                    f"{len(r['bad_cus'])} bad CU(s)" + (f": {bad}" if bad else "")
                 )
                 if not r["ok"]:
                     rc = 1
