@@ -99,12 +99,15 @@ def build_amdhal_asan(force: bool = False) -> str:
 
 def build_hiphealth(force: bool = False) -> str:
     """HIP kernels; rebuilt when the source or a header it includes (the
-    self-test's, the CU footprint's, the per-CU self-test's) changes."""
+    self-test's, the CU footprint's, the per-CU self-test's, the load
+    self-test's) changes."""
     src = os.path.join(CPP_DIR, "hiphealth.hip")
     hdrs = [
         os.path.join(CPP_DIR, "selftest_kernels.hpp"),
         os.path.join(CPP_DIR, "footprint_kernels.hpp"),
         os.path.join(CPP_DIR, "cutest_kernels.hpp"),
+        os.path.join(CPP_DIR, "loadtest_kernels.hpp"),
+        os.path.join(CPP_DIR, "loadtest_core.hpp"),
     ]
     out = os.path.join(PKG_DIR, f"_hiphealth{_ext_suffix()}")
     if force or _needs_build(src, out) or any(_needs_build(h, out) for h in hdrs):
@@ -173,6 +176,26 @@ def build_claimio_selftest(out: str, sanitize: bool = True) -> str:
     Python), by default under AddressSanitizer + UBSan. CPU only; run the
     binary directly."""
     src = os.path.join(CPP_DIR, "claimio_selftest.cpp")
+    flags = ["-g", "-O1", "-std=c++17"]
+    if sanitize:
+        link = sanitizer_link_flags()
+        if link is None:
+            raise RuntimeError("gcc has no ASan/UBSan runtime installed")
+        flags += [
+            "-fsanitize=address,undefined",
+            "-fno-sanitize-recover=undefined",
+            "-fno-omit-frame-pointer",
+        ] + link
+    _run(["g++"] + flags + [src, "-o", out])
+    return out
+
+
+def build_loadtest_core_selftest(out: str, sanitize: bool = True) -> str:
+    """Stand-alone driver of loadtest_core.hpp (the load self-test's operand
+    generator, K bound and checksum; its own ``main``, no Python, no HIP),
+    by default under AddressSanitizer + UBSan. CPU only; run the binary
+    directly."""
+    src = os.path.join(CPP_DIR, "loadtest_core_selftest.cpp")
     flags = ["-g", "-O1", "-std=c++17"]
     if sanitize:
         link = sanitizer_link_flags()

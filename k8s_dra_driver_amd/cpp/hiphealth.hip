@@ -22,6 +22,9 @@
 //   cu_selftest()    - per-CU self-test: an LDS pattern test and the MFMA
 //                      known-answer table on every CU, mismatches named by
 //                      (xcc, se, sh, cu) (cutest_kernels.hpp)
+//   load_selftest()  - load self-test: a tiled bf16 MFMA GEMM on exact data
+//                      for a time budget, every element of every iteration
+//                      compared bit for bit (loadtest_kernels.hpp)
 //
 // Written for gfx950: 64-wide waves, 256 CUs in 8 XCDs (grids sized
 // >> 256 workgroups), 16 B/lane streaming accesses.
@@ -32,7 +35,12 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -663,6 +671,11 @@ py::bytes mfma_burn_probe(int device, int iters, int blocks) {
 #include "cutest_kernels.hpp"
 
 // ---------------------------------------------------------------------------
+// load self-test: tiled bf16 GEMM checked bit for bit under sustained load
+// ---------------------------------------------------------------------------
+#include "loadtest_kernels.hpp"
+
+// ---------------------------------------------------------------------------
 // device info
 // ---------------------------------------------------------------------------
 int device_count() {
@@ -797,4 +810,40 @@ PYBIND11_MODULE(_hiphealth, m) {
         "Returns (guard + blocks x (hw_id, xcc_id, block, simd_mask, "
         "lds_mismatches, mfma_mismatches, 0, 0) uint32 + guard, the dict of "
         "cu_selftest)");
+  m.attr("LOADTEST_MAX_K") = kLtMaxK;
+  m.attr("LOADTEST_BATCH") = kLtBatch;
+  m.attr("LOADTEST_POISON") = kLtPoison;
+  m.attr("LOADTEST_PROBE_MAX_ITERATIONS") = kLtProbeMaxIters;
+  m.def("load_selftest", &load_selftest, py::arg("device") = 0,
+        py::arg("seconds") = 5.0, py::arg("m") = 4096, py::arg("n") = 4096,
+        py::arg("k") = 4096, py::arg("seed") = 0x5E1F7E57C0FFEEull,
+        "Load self-test: A [m][k] and B^T [n][k] bf16 are generated from "
+        "seed, gemm_ref computes the golden C once (its row and column sums "
+        "are checked on the host against the generator), then load_gemm -> "
+        "c_verify run in batches of LOADTEST_BATCH until seconds (in (0, "
+        "600]) have passed or a batch recorded a mismatch. m and n are "
+        "multiples of 128, k a multiple of 64 up to LOADTEST_MAX_K. Returns "
+        "{ok, device, seed, m, n, k, iterations, seconds, checksum_ok, "
+        "checksum_first_bad, mismatches, records: [(iteration, row, col, "
+        "got_bits, want_bits)], bad_tiles: [(tile_row, tile_col, "
+        "mismatches)], bad_cus: [{xcc, se, sh, cu, mismatches}], cus_seen, "
+        "tflops}; tflops is event-timed over the whole loop and informative "
+        "only");
+  m.def("load_gemm_probe", &load_gemm_probe, py::arg("device"), py::arg("a"),
+        py::arg("b_t"), py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("want"), py::arg("iterations"), py::arg("flips"),
+        py::arg("stage"),
+        "The load self-test's kernels on the caller's bf16 operands (a: m x "
+        "k, b_t: n x k uint16). want is the golden C (m x n float32) or "
+        "empty for gemm_ref's; every (element of a, 16-bit mask) of flips is "
+        "XORed in once the golden copy exists. Returns (guard + C + guard, "
+        "report, tile records): stage 'ref' gives gemm_ref's C, 'gemm' one "
+        "load_gemm's C and guard + tiles x (hw_id, xcc_id, tile, 0) uint32 + "
+        "guard, 'verify' C after `iterations` load_gemm -> c_verify (all "
+        "poison), the dict of load_selftest and the records of every "
+        "iteration");
+  m.def("load_operands_probe", &load_operands_probe, py::arg("device"),
+        py::arg("m"), py::arg("n"), py::arg("k"), py::arg("seed"),
+        "load_operands between guards: (guard + A + guard, guard + B^T + "
+        "guard), bf16 bit patterns");
 }

@@ -12,6 +12,7 @@ projection, carve/restore partitions, and run the health probes.
     amd-dra-ctl health --signals     # + ECC / retired-page / thermal signals
     amd-dra-ctl health --selftest    # + HBM pattern / MFMA known-answer test
     amd-dra-ctl health --selftest --per-cu   # + LDS / MFMA test of every CU
+    amd-dra-ctl health --selftest --load-seconds 5   # + checked GEMM under load
 Use ``--hal fake`` anywhere to drive the modeled 8xMI355X node.
 """
 
@@ -191,7 +192,9 @@ def _print_signals(rec: dict) -> None:
         print(f"    unsupported {k}: {why}")
 
 
-def _selftest_into(rec: dict, g, mib: int, per_cu: bool = False) -> None:
+def _selftest_into(
+    rec: dict, g, mib: int, per_cu: bool = False, load_seconds: float = 0.0
+) -> None:
     """Self-test one GPU in a child process and add what it found to the
     GPU's record. The operator vouches that nothing is using the GPU; a
     partitioned GPU, or one without a PCI address, is skipped."""
@@ -200,7 +203,10 @@ def _selftest_into(rec: dict, g, mib: int, per_cu: bool = False) -> None:
     if g.compute_partition.upper() != "SPX" or g.partitions or not g.pcie_bdf:
         rec["selftest"] = {"result": "skipped"}
         return
-    res = selftest.run(g, mib=mib, **({"per_cu": True} if per_cu else {}))
+    extra = {"per_cu": True} if per_cu else {}
+    if load_seconds > 0:
+        extra["load_seconds"] = load_seconds
+    res = selftest.run(g, mib=mib, **extra)
     rec["selftest"] = {
         "result": res.outcome,
         "seconds": round(res.seconds, 3),
@@ -212,6 +218,16 @@ def _selftest_into(rec: dict, g, mib: int, per_cu: bool = False) -> None:
             "covered": cu["covered"],
             "expected": cu["multi_processor_count"],
             "bad_cus": cu["bad_cus"],
+        }
+    load = (res.report or {}).get("load") if load_seconds > 0 else None
+    if load:
+        rec["selftest"]["load"] = {
+            "iterations": load["iterations"],
+            "mismatches": load["mismatches"],
+            "checksum_ok": load["checksum_ok"],
+            "cus_seen": load["cus_seen"],
+            "tflops": load["tflops"],
+            "bad_cus": load["bad_cus"],
         }
     rec["findings"] += [
         {"reason": f.reason, "severity": f.severity, "detail": f.detail}
@@ -226,7 +242,9 @@ def cmd_health(args) -> int:
     for g in lib.enumerate():
         rec = _health_record(lib, g)
         if args.selftest:
-            _selftest_into(rec, g, args.selftest_mib, args.per_cu)
+            _selftest_into(
+                rec, g, args.selftest_mib, args.per_cu, args.load_seconds
+            )
         records.append(rec)
         if not args.json:
             print(f"{g.canonical_name}: {rec['health']}")
@@ -250,6 +268,15 @@ def cmd_health(args) -> int:
                             f"cu {c['cu']}: lds {c['lds_mismatches']}, "
                             f"mfma {c['mfma_mismatches']}"
                         )
+                if "load" in st:
+                    load = st["load"]
+                    print(
+                        f"    load: {load['iterations']} iteration(s), "
+                        f"{load['mismatches']} mismatch(es), checksum "
+                        f"{'ok' if load['checksum_ok'] else 'FAILED'}, "
+                        f"{load['cus_seen']} CUs seen, "
+                        f"{load['tflops']:.0f} TF/s (informative)"
+                    )
                 if not args.signals:
                     for f in rec["findings"]:
                         if f["reason"].startswith("Selftest"):
@@ -350,6 +377,14 @@ def main(argv=None) -> int:
         action="store_true",
         help="with --selftest, also test the LDS and the matrix pipes of "
         "every compute unit and name the CUs that fail",
+    )
+    hp.add_argument(
+        "--load-seconds",
+        type=float,
+        default=0.0,
+        help="with --selftest, also run a tiled bf16 GEMM on exact data for "
+        "this many seconds per GPU and compare every element of every "
+        "iteration bit for bit (0 = off)",
     )
     hp.add_argument(
         "--selftest-mib",

@@ -153,6 +153,19 @@ class PluginMetrics:
             ["gpu"],
             registry=self.registry,
         )
+        # its load stage, set only when that stage ran
+        self.gpu_selftest_load_iterations = Gauge(
+            "dra_gpu_selftest_load_iterations",
+            "GEMM iterations the last startup load self-test ran and verified",
+            ["gpu"],
+            registry=self.registry,
+        )
+        self.gpu_selftest_load_mismatches = Gauge(
+            "dra_gpu_selftest_load_mismatches",
+            "Mismatching values in the last startup load self-test",
+            ["gpu"],
+            registry=self.registry,
+        )
         #: gpu label -> reason label currently exported as dra_gpu_unhealthy
         self._unhealthy_reason = {}
 

@@ -227,6 +227,7 @@ class Driver:
         mib: int = 1024,
         timeout_s: float = 120.0,
         per_cu: bool = False,
+        load_seconds: float = 0,
     ) -> Dict[int, str]:
         """Self-test every GPU in scope that nothing is using, one after
         another, and hand the findings to the health monitor. Meant for
@@ -236,6 +237,9 @@ class Driver:
         with result in pass | memory | compute | error | skipped.
         ``per_cu`` adds the per-CU stage (LDS and matrix pipes of every
         compute unit); only then is the runner called with ``per_cu=True``.
+        A positive ``load_seconds`` adds the load stage (a tiled bf16 GEMM
+        checked bit for bit for that long); only then is the runner called
+        with ``load_seconds``.
 
         A GPU is skipped (logged, no finding) when a claim recovered from
         the checkpoints holds it, when it is partitioned, or when it has
@@ -265,12 +269,16 @@ class Driver:
                 continue
             t0 = time.perf_counter()
             extra = {"per_cu": True} if per_cu else {}
-            cu = None
+            if load_seconds and load_seconds > 0:
+                extra["load_seconds"] = load_seconds
+            cu = load = None
             try:
                 res = runner(gpu, mib=mib, timeout_s=timeout_s, **extra)
                 outcome, findings = res.outcome, res.findings()
                 if per_cu:
                     cu = (res.report or {}).get("cu")
+                if "load_seconds" in extra:
+                    load = (res.report or {}).get("load")
             except Exception as e:
                 log.exception("gpu-%d: startup self-test failed to run", idx)
                 from .health import HealthFinding, SOFT
@@ -287,6 +295,13 @@ class Driver:
                 )
                 self.metrics.gpu_selftest_cus_bad.labels(str(idx)).set(
                     len(cu["bad_cus"])
+                )
+            if load:
+                self.metrics.gpu_selftest_load_iterations.labels(str(idx)).set(
+                    load["iterations"]
+                )
+                self.metrics.gpu_selftest_load_mismatches.labels(str(idx)).set(
+                    load["mismatches"]
                 )
             self.health.set_selftest_findings(idx, findings)
             if findings:

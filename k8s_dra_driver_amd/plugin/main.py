@@ -154,6 +154,15 @@ def build_parser() -> argparse.ArgumentParser:
         "pipes of every compute unit and name the CUs that fail",
     )
     p.add_argument(
+        "--selftest-load-seconds",
+        type=float,
+        default=float(_env("SELFTEST_LOAD_SECONDS", "0")),
+        help="with --startup-selftest on, also run a tiled bf16 GEMM on exact "
+        "data on every CU for this many seconds per GPU and compare every "
+        "element of every iteration bit for bit (0 = off); the time is added "
+        "to --selftest-timeout-s",
+    )
+    p.add_argument(
         "--selftest-timeout-s",
         type=float,
         default=float(_env("SELFTEST_TIMEOUT_S", "120")),
@@ -205,6 +214,8 @@ def startup_selftest(args, driver) -> bool:
     if args.startup_selftest != "on":
         return False
     extra = {"per_cu": True} if args.selftest_per_cu == "on" else {}
+    if args.selftest_load_seconds > 0:
+        extra["load_seconds"] = args.selftest_load_seconds
     driver.run_startup_selftest(
         mib=args.selftest_mib, timeout_s=args.selftest_timeout_s, **extra
     )

@@ -16,7 +16,10 @@ Two halves:
   plugin. With ``--per-cu`` it goes on to ``_hiphealth.cu_selftest`` (LDS
   pattern test and the whole known-answer table on every compute unit) and
   puts that result under ``"cu"``: a mismatch then carries the name of the
-  CU it happened on.
+  CU it happened on. With ``--load-seconds S`` it goes on to
+  ``_hiphealth.load_selftest``: a tiled bf16 MFMA GEMM on exact data runs for
+  S seconds, every element of every iteration is compared bit for bit, and
+  the result goes under ``"load"``.
 - **parent** (:func:`run`): starts that child in a fresh process with a
   timeout, one child at a time, and turns what it says into a
   :class:`SelftestResult`. The calling process never initialises HIP, so a
@@ -40,6 +43,11 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
 DEFAULT_MIB = 1024
 DEFAULT_TIMEOUT_S = 120.0
+#: added to the child's time limit with the load stage, on top of its
+#: seconds: generating the operands, the golden product on the vector ALUs
+#: and its checksum on the host
+LOAD_GOLDEN_ALLOWANCE_S = 60.0
+MAX_LOAD_SECONDS = 600.0
 
 EXIT_PASS = 0
 EXIT_MISMATCH = 1
@@ -114,6 +122,9 @@ class SelftestResult:
         cu = report.get("cu") or {}
         if cu.get("bad_cus"):
             out.append(finding("SelftestComputeMismatch", _cu_detail(cu)))
+        load = report.get("load") or {}
+        if load and not load.get("ok", True):
+            out.append(finding("SelftestComputeMismatch", _load_detail(load)))
         return out
 
 
@@ -150,6 +161,74 @@ def _cu_detail(cu: dict) -> str:
     return detail
 
 
+def _load_detail(load: dict) -> str:
+    """The load part of a report as one finding's text: how long it ran, how
+    many values were wrong, the first few bad CUs by name and the lowest
+    record."""
+    detail = (
+        f"load test: {load['mismatches']} mismatching value(s) in "
+        f"{load['iterations']} iteration(s) of "
+        f"{load['m']}x{load['n']}x{load['k']}"
+    )
+    if not load["checksum_ok"]:
+        detail += (
+            "; golden product failed its checksum at "
+            f"{load['checksum_first_bad'] or 'an unnamed place'}"
+        )
+    bad = load["bad_cus"]
+    if bad:
+        detail += f"; {len(bad)} of {load['cus_seen']} CU(s) seen bad: "
+        detail += ", ".join(
+            f"xcc {c['xcc']} se {c['se']} sh {c['sh']} cu {c['cu']} "
+            f"({c['mismatches']})"
+            for c in bad[:MAX_CUS_IN_DETAIL]
+        )
+        if len(bad) > MAX_CUS_IN_DETAIL:
+            detail += f", and {len(bad) - MAX_CUS_IN_DETAIL} more"
+    if load["records"]:
+        it, row, col, got, want = min(load["records"])
+        detail += (
+            f"; first recorded value: iteration {it} row {row} col {col}: "
+            f"got 0x{got:08x}, want 0x{want:08x}"
+        )
+    return detail
+
+
+def _classify_load(load) -> bool:
+    """True when the load part of a report is bad (a mismatch or a failed
+    checksum of the golden product); raises on a part that does not have the
+    documented shape."""
+    if not isinstance(load, dict):
+        raise TypeError("load is not an object")
+    for key in ("m", "n", "k", "iterations", "mismatches", "cus_seen"):
+        load[key] = int(load[key])
+    if not isinstance(load["ok"], bool) or not isinstance(load["checksum_ok"], bool):
+        raise TypeError("load: ok and checksum_ok must be booleans")
+    load["checksum_first_bad"] = str(load.get("checksum_first_bad", ""))
+    load["tflops"] = float(load["tflops"])
+    load["records"] = [tuple(int(v) for v in r) for r in load["records"]]
+    if any(len(r) != 5 for r in load["records"]):
+        raise ValueError("a record of load does not have 5 fields")
+    load["bad_tiles"] = [tuple(int(v) for v in t) for t in load["bad_tiles"]]
+    if any(len(t) != 3 for t in load["bad_tiles"]):
+        raise ValueError("a bad tile of load does not have 3 fields")
+    names = ("xcc", "se", "sh", "cu", "mismatches")
+    load["bad_cus"] = [{k: int(c[k]) for k in names} for c in load["bad_cus"]]
+    mismatched = bool(load["mismatches"])
+    if (
+        mismatched != bool(load["bad_cus"])
+        or mismatched != bool(load["records"])
+        or mismatched != bool(load["bad_tiles"])
+        or load["ok"] != (not mismatched and load["checksum_ok"])
+    ):
+        raise ValueError(
+            "load: ok, mismatches, checksum_ok and bad_cus disagree"
+        )
+    if load["iterations"] < 1:
+        raise ValueError("load: no iteration ran")
+    return not load["ok"]
+
+
 def _classify_cu(cu) -> bool:
     """True when the per-CU part of a report lists a mismatch; raises on a
     part that does not have the documented shape."""
@@ -179,6 +258,8 @@ def _classify(report: dict) -> str:
     memory_bad = any(int(p["mismatches"]) for p in report["memory"])
     compute_bad = bool(int(report["mfma"]["mismatches"]))
     if "cu" in report and _classify_cu(report["cu"]):
+        compute_bad = True
+    if "load" in report and _classify_load(report["load"]):
         compute_bad = True
     for part in list(report["memory"]) + [report["mfma"]]:
         part["records"] = [tuple(int(v) for v in r) for r in part["records"]]
@@ -226,12 +307,16 @@ def run(
     timeout_s: float = DEFAULT_TIMEOUT_S,
     spawn: Spawn = _spawn_child,
     per_cu: bool = False,
+    load_seconds: float = 0.0,
 ) -> SelftestResult:
     """Self-test one GPU (a ``hal.model.GpuInfo``: ``index`` and
     ``pcie_bdf`` are used) in a child process; ``per_cu`` adds the per-CU
-    stage. Never raises and never retries: whatever goes wrong is an
-    ``error`` result."""
+    stage, a positive ``load_seconds`` the load stage of that length, which
+    extends the child's time limit by as much plus
+    ``LOAD_GOLDEN_ALLOWANCE_S``. Never raises and never retries: whatever
+    goes wrong is an ``error`` result."""
     bdf = gpu.pcie_bdf
+    load_seconds = float(load_seconds)
     argv = [
         sys.executable,
         "-m",
@@ -244,6 +329,10 @@ def run(
     ]
     if per_cu:
         argv.append("--per-cu")
+    with_load = load_seconds > 0
+    if with_load:
+        argv += ["--load-seconds", f"{load_seconds:g}"]
+        timeout_s = timeout_s + load_seconds + LOAD_GOLDEN_ALLOWANCE_S
 
     def result(outcome, report=None, error=""):
         return SelftestResult(
@@ -284,6 +373,8 @@ def run(
         try:
             if per_cu and "cu" not in report:
                 raise KeyError("cu")
+            if with_load and "load" not in report:
+                raise KeyError("load")
             outcome = _classify(report)
         except (KeyError, TypeError, ValueError) as e:
             return result("error", error=f"exit {rc}, malformed report: {e!r}")
@@ -297,7 +388,9 @@ def run(
 # ---------------------------------------------------------------------------
 # child
 # ---------------------------------------------------------------------------
-def _child(bdf: str, mib: int, per_cu: bool = False) -> Tuple[int, dict]:
+def _child(
+    bdf: str, mib: int, per_cu: bool = False, load_seconds: float = 0.0
+) -> Tuple[int, dict]:
     try:
         from k8s_dra_driver_amd import _hiphealth
 
@@ -312,6 +405,11 @@ def _child(bdf: str, mib: int, per_cu: bool = False) -> Tuple[int, dict]:
                 if per_cu:
                     report["cu"] = _hiphealth.cu_selftest(ordinal)
                     report["ok"] = bool(report["ok"] and report["cu"]["ok"])
+                if load_seconds > 0:
+                    report["load"] = _hiphealth.load_selftest(
+                        ordinal, seconds=load_seconds
+                    )
+                    report["ok"] = bool(report["ok"] and report["load"]["ok"])
                 return (EXIT_PASS if report["ok"] else EXIT_MISMATCH), report
         return EXIT_ERROR, {
             "ok": False,
@@ -333,10 +431,20 @@ def main(argv=None) -> int:
         action="store_true",
         help="also test every compute unit's LDS and matrix pipes, by name",
     )
+    ap.add_argument(
+        "--load-seconds",
+        type=float,
+        default=0.0,
+        help="also run the load test (a tiled bf16 GEMM on exact data, "
+        "every element of every iteration compared) for this long; 0 = off",
+    )
     ap.add_argument("--json", action="store_true", help="print the full report")
     args = ap.parse_args(argv)
     t0 = time.monotonic()
-    rc, report = _child(args.bdf, args.mib, args.per_cu)
+    if args.load_seconds < 0 or args.load_seconds > MAX_LOAD_SECONDS:
+        ap.error(f"--load-seconds must be in [0, {MAX_LOAD_SECONDS:g}]")
+    extra = {"load_seconds": args.load_seconds} if args.load_seconds > 0 else {}
+    rc, report = _child(args.bdf, args.mib, args.per_cu, **extra)
     report["seconds"] = round(time.monotonic() - t0, 3)
     if args.json:
         print(json.dumps(report, sort_keys=True))
@@ -357,6 +465,16 @@ def main(argv=None) -> int:
                 f"{cu['multi_processor_count']} CUs covered, "
                 f"{len(cu['bad_cus'])} bad; lds {cu['lds']['mismatches']} "
                 f"mismatch(es), mfma {cu['mfma']['mismatches']} mismatch(es)"
+            )
+        if "load" in report:
+            load = report["load"]
+            print(
+                f"{args.bdf}: load: {load['iterations']} iteration(s) of "
+                f"{load['m']}x{load['n']}x{load['k']} in "
+                f"{load['seconds']:.1f}s on {load['cus_seen']} CUs, "
+                f"{load['mismatches']} mismatch(es), checksum "
+                f"{'ok' if load['checksum_ok'] else 'FAILED'}; "
+                f"{load['tflops']:.0f} TF/s (informative)"
             )
     return rc
 

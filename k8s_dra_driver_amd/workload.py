@@ -176,6 +176,15 @@ def main(argv=None) -> int:
         "mismatch",
     )
     ap.add_argument(
+        "--load-selftest",
+        type=float,
+        default=0.0,
+        metavar="SECONDS",
+        help="run a tiled bf16 GEMM on exact data on every visible device "
+        "for this long, compare every element of every iteration bit for "
+        "bit and name the tiles and CUs that fail; exit 1 on a mismatch",
+    )
+    ap.add_argument(
         "--cu-footprint",
         action="store_true",
         help="print which compute units this process's blocks run on, per "
@@ -196,6 +205,7 @@ def main(argv=None) -> int:
         or args.nbody
         or args.selftest
         or args.cu_selftest
+        or args.load_selftest
         or args.cu_footprint
     ):
         from k8s_dra_driver_amd import _hiphealth
@@ -241,6 +251,23 @@ def main(argv=None) -> int:
                     f"covered by {r['blocks']} blocks, lds "
                     f"{r['lds']['mismatches']} mismatch(es), mfma "
                     f"{r['mfma']['mismatches']} mismatch(es), "
+                    f"{len(r['bad_cus'])} bad CU(s)" + (f": {bad}" if bad else "")
+                )
+                if not r["ok"]:
+                    rc = 1
+            if args.load_selftest:
+                r = _hiphealth.load_selftest(d, seconds=args.load_selftest)
+                bad = ", ".join(
+                    f"xcc {c['xcc']} se {c['se']} sh {c['sh']} cu {c['cu']}"
+                    for c in r["bad_cus"]
+                )
+                print(
+                    f"device {d}: load-selftest {'ok' if r['ok'] else 'FAILED'}: "
+                    f"{r['iterations']} iteration(s) of "
+                    f"{r['m']}x{r['n']}x{r['k']} in {r['seconds']:.1f}s on "
+                    f"{r['cus_seen']} CUs, {r['mismatches']} mismatch(es), "
+                    f"checksum {'ok' if r['checksum_ok'] else 'FAILED'}, "
+                    f"{r['tflops']:.0f} TF/s (informative), "
                     f"{len(r['bad_cus'])} bad CU(s)" + (f": {bad}" if bad else "")
                 )
                 if not r["ok"]:
