@@ -25,6 +25,9 @@
 //   load_selftest()  - load self-test: a tiled bf16 MFMA GEMM on exact data
 //                      for a time budget, every element of every iteration
 //                      compared bit for bit (loadtest_kernels.hpp)
+//   mx_selftest()    - the same on the block-scaled MFMA
+//                      (v_mfma_scale_f32_16x16x128_f8f6f4) with mxfp8 or
+//                      mxfp4 operands and E8M0 scales (mxtest_kernels.hpp)
 //
 // Written for gfx950: 64-wide waves, 256 CUs in 8 XCDs (grids sized
 // >> 256 workgroups), 16 B/lane streaming accesses.
@@ -676,6 +679,11 @@ py::bytes mfma_burn_probe(int device, int iters, int blocks) {
 #include "loadtest_kernels.hpp"
 
 // ---------------------------------------------------------------------------
+// MX load self-test: tiled mxfp8 / mxfp4 GEMM on the block-scaled MFMA
+// ---------------------------------------------------------------------------
+#include "mxtest_kernels.hpp"
+
+// ---------------------------------------------------------------------------
 // device info
 // ---------------------------------------------------------------------------
 int device_count() {
@@ -846,4 +854,56 @@ PYBIND11_MODULE(_hiphealth, m) {
         py::arg("m"), py::arg("n"), py::arg("k"), py::arg("seed"),
         "load_operands between guards: (guard + A + guard, guard + B^T + "
         "guard), bf16 bit patterns");
+  {
+    py::list formats;
+    py::dict max_k;
+    for (int f = 0; f < kMxFormats; ++f) {
+      formats.append(mx_format_name(f));
+      max_k[mx_format_name(f)] = mx_max_k(f);
+    }
+    m.attr("MXTEST_FORMATS") = py::tuple(formats);
+    m.attr("MXTEST_MAX_K") = max_k;
+  }
+  m.def("mx_selftest", &mx_selftest, py::arg("device"), py::arg("format"),
+        py::arg("seconds"), py::arg("m") = 4096, py::arg("n") = 4096,
+        py::arg("k") = 4096, py::arg("seed") = 0x5E1F7E57C0FFEEull,
+        "MX load self-test for format 'mxfp8' (e4m3 elements) or 'mxfp4' "
+        "(e2m1): A [m][k] and B^T [n][k] with one E8M0 scale per 32 k of a "
+        "row are generated from seed, mx_gemm_ref computes the golden C once "
+        "without MFMA (its row and column sums are checked on the host "
+        "against the generator), then mx_gemm (v_mfma_scale_f32_16x16x128_"
+        "f8f6f4) -> c_verify run in batches of LOADTEST_BATCH until seconds "
+        "(in (0, 600]) have passed or a batch recorded a mismatch. m and n "
+        "are multiples of 128, k a multiple of 128 up to "
+        "MXTEST_MAX_K[format]. Returns the dict of load_selftest plus "
+        "format and golden_seconds (golden kernel and host checksum, "
+        "informative only)");
+  m.def("mx_gemm_probe", &mx_gemm_probe, py::arg("device"), py::arg("format"),
+        py::arg("a"), py::arg("a_scales"), py::arg("b_t"),
+        py::arg("b_t_scales"), py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("want"), py::arg("iterations"), py::arg("flips"),
+        py::arg("stage"),
+        "The MX load self-test's kernels on the caller's operands (a: m "
+        "rows, b_t: n rows of k packed elements: k bytes of e4m3 or k / 2 "
+        "bytes of e2m1, the even k in the low nibble; scales: rows x k / 32 "
+        "E8M0 bytes). want is the golden C (m x n float32) or empty for "
+        "mx_gemm_ref's; every (byte of a, 8-bit mask) of flips is XORed in "
+        "once the golden copy exists. Returns (guard + C + guard, report, "
+        "tile records) per stage 'ref', 'gemm' or 'verify' as "
+        "load_gemm_probe does");
+  m.def("mx_operands_probe", &mx_operands_probe, py::arg("device"),
+        py::arg("format"), py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("seed"),
+        "mx_operands between guards: (A, A's scales, B^T, B^T's scales), "
+        "each guard + bytes + guard");
+  m.def("mx_mfma_probe", &mx_mfma_probe, py::arg("device"), py::arg("format"),
+        py::arg("a"), py::arg("a_scales"), py::arg("b_t"),
+        py::arg("b_t_scales"), py::arg("c"), py::arg("opsel") = 0,
+        py::arg("other_scale") = 127,
+        "One wave, one v_mfma_scale_f32_16x16x128_f8f6f4: a and b_t are "
+        "[16][128] packed elements, the scales [16][4] E8M0 bytes (row, "
+        "block of 32 k), c [16][16] float32; the binding applies the lane "
+        "map. The scales travel in byte opsel of the scale registers, whose "
+        "other bytes hold other_scale. Returns guard + D[16][16] float32 + "
+        "guard");
 }

@@ -20,6 +20,7 @@
 #pragma once
 
 #include <chrono>
+#include <functional>
 #include <set>
 
 #include "loadtest_core.hpp"
@@ -265,8 +266,6 @@ void launch_load_gemm(const lt_bf16* a, const lt_bf16* bt, float* c, int m,
 }
 
 struct LoadBuffers {
-  const lt_bf16* a;
-  const lt_bf16* bt;
   float* c;
   const float* golden;
   // `slots` iterations' worth of per-tile records and mismatch counters;
@@ -287,13 +286,17 @@ struct LoadOutcome {
   double seconds = 0;
 };
 
-// load_gemm -> c_verify in batches of kLtBatch, one synchronisation per
-// batch, until `seconds` of wall time have passed (max_iters < 0) or
-// max_iters iterations ran; always at least one batch, and none after a
-// batch that recorded a mismatch.
-void run_load_loop(const LoadBuffers& buf, int m, int n, int k,
-                   double seconds, long long max_iters, const char* what,
-                   LoadOutcome* out) {
+// Launches the GEMM under test once: it writes all of buf.c and one record
+// per tile to the slot it is handed.
+typedef std::function<void(FootRecord*)> LoadGemm;
+
+// gemm -> c_verify in batches of kLtBatch, one synchronisation per batch,
+// until `seconds` of wall time have passed (max_iters < 0) or max_iters
+// iterations ran; always at least one batch, and none after a batch that
+// recorded a mismatch.
+void run_load_loop(const LoadBuffers& buf, const LoadGemm& gemm, int m, int n,
+                   int k, double seconds, long long max_iters,
+                   const char* what, LoadOutcome* out) {
   const int tiles = (m / kLtTile) * (n / kLtTile);
   const int verify_blocks =
       (int)std::min<size_t>(1024, ((size_t)m * n / 4 + 255) / 256);
@@ -318,7 +321,7 @@ void run_load_loop(const LoadBuffers& buf, int m, int n, int k,
     for (long long b = 0; b < batch; ++b) {
       u64 it = out->iterations + b;
       size_t slot = (size_t)(it % buf.slots) * tiles;
-      launch_load_gemm(buf.a, buf.bt, buf.c, m, n, k, rec_dev + slot);
+      gemm(rec_dev + slot);
       hipLaunchKernelGGL(c_verify, dim3(verify_blocks), dim3(256), 0, 0,
                          reinterpret_cast<u32x4*>(buf.c),
                          reinterpret_cast<const u32x4*>(buf.golden), m, n,
@@ -453,12 +456,16 @@ py::dict load_selftest(int device, double seconds, int m, int n, int k,
   LoadReport zero;
   std::memset(&zero, 0, sizeof zero);
   GuardedBuf report(sizeof zero, &zero);
-  LoadBuffers buf = {a.as<const lt_bf16>(), bt.as<const lt_bf16>(),
-                     c.as<float>(),         golden.as<const float>(),
-                     &tile_rec,             &tile_bad,
-                     &report,               kLtBatch};
+  LoadBuffers buf = {c.as<float>(), golden.as<const float>(), &tile_rec,
+                     &tile_bad,     &report,                  kLtBatch};
   LoadOutcome out;
-  run_load_loop(buf, m, n, k, seconds, -1, "load_selftest", &out);
+  run_load_loop(
+      buf,
+      [&](FootRecord* rec) {
+        launch_load_gemm(a.as<const lt_bf16>(), bt.as<const lt_bf16>(),
+                         c.as<float>(), m, n, k, rec);
+      },
+      m, n, k, seconds, -1, "load_selftest", &out);
   return load_dict(device, seed, m, n, k, out, sum);
 }
 
@@ -537,16 +544,18 @@ py::tuple load_gemm_probe(
   LoadReport zero;
   std::memset(&zero, 0, sizeof zero);
   GuardedBuf report(sizeof zero, &zero);
-  LoadBuffers buf = {da.payload<const lt_bf16>(),
-                     dbt.payload<const lt_bf16>(),
-                     dc.payload<float>(),
-                     golden.payload<const float>(),
-                     &tile_rec,
-                     &tile_bad,
-                     &report,
-                     iterations};
+  LoadBuffers buf = {dc.payload<float>(), golden.payload<const float>(),
+                     &tile_rec,           &tile_bad,
+                     &report,             iterations};
   LoadOutcome out;
-  run_load_loop(buf, m, n, k, 0.0, iterations, "load_gemm_probe", &out);
+  run_load_loop(
+      buf,
+      [&](FootRecord* rec) {
+        launch_load_gemm(da.payload<const lt_bf16>(),
+                         dbt.payload<const lt_bf16>(), dc.payload<float>(), m,
+                         n, k, rec);
+      },
+      m, n, k, 0.0, iterations, "load_gemm_probe", &out);
   // the caller's operands have no seed: nothing to check a checksum against
   py::dict d = load_dict(device, 0, m, n, k, out, LtChecksum());
   return py::make_tuple(dc.download(), d, tile_rec.download());

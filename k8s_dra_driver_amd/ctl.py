@@ -13,6 +13,8 @@ projection, carve/restore partitions, and run the health probes.
     amd-dra-ctl health --selftest    # + HBM pattern / MFMA known-answer test
     amd-dra-ctl health --selftest --per-cu   # + LDS / MFMA test of every CU
     amd-dra-ctl health --selftest --load-seconds 5   # + checked GEMM under load
+    amd-dra-ctl health --selftest --load-seconds 5 --load-formats mxfp8,mxfp4
+                                     # + the same on the block-scaled MFMA
 Use ``--hal fake`` anywhere to drive the modeled 8xMI355X node.
 """
 
@@ -192,8 +194,23 @@ def _print_signals(rec: dict) -> None:
         print(f"    unsupported {k}: {why}")
 
 
+def _load_formats(text: str):
+    """argparse type of --load-formats: a tuple of MX format names."""
+    from . import selftest
+
+    try:
+        return selftest.parse_load_formats(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def _selftest_into(
-    rec: dict, g, mib: int, per_cu: bool = False, load_seconds: float = 0.0
+    rec: dict,
+    g,
+    mib: int,
+    per_cu: bool = False,
+    load_seconds: float = 0.0,
+    load_formats=(),
 ) -> None:
     """Self-test one GPU in a child process and add what it found to the
     GPU's record. The operator vouches that nothing is using the GPU; a
@@ -206,6 +223,8 @@ def _selftest_into(
     extra = {"per_cu": True} if per_cu else {}
     if load_seconds > 0:
         extra["load_seconds"] = load_seconds
+    if load_formats:
+        extra["load_formats"] = tuple(load_formats)
     res = selftest.run(g, mib=mib, **extra)
     rec["selftest"] = {
         "result": res.outcome,
@@ -229,6 +248,19 @@ def _selftest_into(
             "tflops": load["tflops"],
             "bad_cus": load["bad_cus"],
         }
+    load_mx = (res.report or {}).get("load_mx") if load_formats else None
+    if load_mx:
+        rec["selftest"]["load_mx"] = {
+            fmt: {
+                "iterations": part["iterations"],
+                "mismatches": part["mismatches"],
+                "checksum_ok": part["checksum_ok"],
+                "cus_seen": part["cus_seen"],
+                "tflops": part["tflops"],
+                "bad_cus": part["bad_cus"],
+            }
+            for fmt, part in load_mx.items()
+        }
     rec["findings"] += [
         {"reason": f.reason, "severity": f.severity, "detail": f.detail}
         for f in res.findings()
@@ -243,7 +275,12 @@ def cmd_health(args) -> int:
         rec = _health_record(lib, g)
         if args.selftest:
             _selftest_into(
-                rec, g, args.selftest_mib, args.per_cu, args.load_seconds
+                rec,
+                g,
+                args.selftest_mib,
+                args.per_cu,
+                args.load_seconds,
+                args.load_formats,
             )
         records.append(rec)
         if not args.json:
@@ -276,6 +313,14 @@ def cmd_health(args) -> int:
                         f"{'ok' if load['checksum_ok'] else 'FAILED'}, "
                         f"{load['cus_seen']} CUs seen, "
                         f"{load['tflops']:.0f} TF/s (informative)"
+                    )
+                for fmt, part in st.get("load_mx", {}).items():
+                    print(
+                        f"    load {fmt}: {part['iterations']} iteration(s), "
+                        f"{part['mismatches']} mismatch(es), checksum "
+                        f"{'ok' if part['checksum_ok'] else 'FAILED'}, "
+                        f"{part['cus_seen']} CUs seen, "
+                        f"{part['tflops']:.0f} TF/s (informative)"
                     )
                 if not args.signals:
                     for f in rec["findings"]:
@@ -387,6 +432,15 @@ def main(argv=None) -> int:
         "iteration bit for bit (0 = off)",
     )
     hp.add_argument(
+        "--load-formats",
+        type=_load_formats,
+        default=(),
+        metavar="FORMAT[,FORMAT]",
+        help="with --load-seconds, run the load test again on the "
+        "block-scaled MFMA for each of these MX formats (mxfp8, mxfp4), "
+        "--load-seconds each",
+    )
+    hp.add_argument(
         "--selftest-mib",
         type=int,
         default=1024,
@@ -400,6 +454,10 @@ def main(argv=None) -> int:
     prof.add_argument("--port", type=int, default=8083)
     prof.add_argument("--seconds", type=float, default=5.0)
     args = ap.parse_args(argv)
+    if args.cmd == "health" and args.load_formats and not (
+        args.selftest and args.load_seconds > 0
+    ):
+        ap.error("--load-formats needs --selftest and a positive --load-seconds")
     return {
         "list": cmd_list,
         "topology": cmd_topology,

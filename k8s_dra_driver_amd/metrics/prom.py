@@ -166,6 +166,20 @@ class PluginMetrics:
             ["gpu"],
             registry=self.registry,
         )
+        # its MX load stages, one series per format that ran
+        self.gpu_selftest_mx_iterations = Gauge(
+            "dra_gpu_selftest_mx_iterations",
+            "Block-scaled GEMM iterations the last startup MX load self-test "
+            "ran and verified",
+            ["gpu", "format"],
+            registry=self.registry,
+        )
+        self.gpu_selftest_mx_mismatches = Gauge(
+            "dra_gpu_selftest_mx_mismatches",
+            "Mismatching values in the last startup MX load self-test",
+            ["gpu", "format"],
+            registry=self.registry,
+        )
         #: gpu label -> reason label currently exported as dra_gpu_unhealthy
         self._unhealthy_reason = {}
 

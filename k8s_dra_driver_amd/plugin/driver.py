@@ -228,6 +228,7 @@ class Driver:
         timeout_s: float = 120.0,
         per_cu: bool = False,
         load_seconds: float = 0,
+        load_formats=(),
     ) -> Dict[int, str]:
         """Self-test every GPU in scope that nothing is using, one after
         another, and hand the findings to the health monitor. Meant for
@@ -239,7 +240,10 @@ class Driver:
         compute unit); only then is the runner called with ``per_cu=True``.
         A positive ``load_seconds`` adds the load stage (a tiled bf16 GEMM
         checked bit for bit for that long); only then is the runner called
-        with ``load_seconds``.
+        with ``load_seconds``. A non-empty ``load_formats`` (MX format
+        names, e.g. ``("mxfp8", "mxfp4")``) runs the load stage again on the
+        block-scaled MFMA for each of them; only then is the runner called
+        with ``load_formats``.
 
         A GPU is skipped (logged, no finding) when a claim recovered from
         the checkpoints holds it, when it is partitioned, or when it has
@@ -271,7 +275,9 @@ class Driver:
             extra = {"per_cu": True} if per_cu else {}
             if load_seconds and load_seconds > 0:
                 extra["load_seconds"] = load_seconds
-            cu = load = None
+            if load_formats:
+                extra["load_formats"] = tuple(load_formats)
+            cu = load = load_mx = None
             try:
                 res = runner(gpu, mib=mib, timeout_s=timeout_s, **extra)
                 outcome, findings = res.outcome, res.findings()
@@ -279,6 +285,8 @@ class Driver:
                     cu = (res.report or {}).get("cu")
                 if "load_seconds" in extra:
                     load = (res.report or {}).get("load")
+                if "load_formats" in extra:
+                    load_mx = (res.report or {}).get("load_mx")
             except Exception as e:
                 log.exception("gpu-%d: startup self-test failed to run", idx)
                 from .health import HealthFinding, SOFT
@@ -302,6 +310,13 @@ class Driver:
                 )
                 self.metrics.gpu_selftest_load_mismatches.labels(str(idx)).set(
                     load["mismatches"]
+                )
+            for fmt, part in (load_mx or {}).items():
+                self.metrics.gpu_selftest_mx_iterations.labels(str(idx), fmt).set(
+                    part["iterations"]
+                )
+                self.metrics.gpu_selftest_mx_mismatches.labels(str(idx), fmt).set(
+                    part["mismatches"]
                 )
             self.health.set_selftest_findings(idx, findings)
             if findings:

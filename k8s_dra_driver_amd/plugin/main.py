@@ -163,6 +163,14 @@ def build_parser() -> argparse.ArgumentParser:
         "to --selftest-timeout-s",
     )
     p.add_argument(
+        "--selftest-load-formats",
+        default=_env("SELFTEST_LOAD_FORMATS", ""),
+        help="with --selftest-load-seconds, run the load stage again on the "
+        "block-scaled MFMA for each of these MX formats (comma-separated: "
+        "mxfp8, mxfp4), --selftest-load-seconds each; the time is added to "
+        "--selftest-timeout-s (empty = off)",
+    )
+    p.add_argument(
         "--selftest-timeout-s",
         type=float,
         default=float(_env("SELFTEST_TIMEOUT_S", "120")),
@@ -207,6 +215,20 @@ def require_selftest_extension(args) -> None:
         )
 
 
+def selftest_load_formats(args) -> tuple:
+    """--selftest-load-formats as a tuple of MX format names; raises
+    ValueError on an unknown name, or when formats are named without a
+    positive --selftest-load-seconds."""
+    from .. import selftest
+
+    formats = selftest.parse_load_formats(args.selftest_load_formats)
+    if formats and not args.selftest_load_seconds > 0:
+        raise ValueError(
+            "--selftest-load-formats needs a positive --selftest-load-seconds"
+        )
+    return formats
+
+
 def startup_selftest(args, driver) -> bool:
     """Run the startup self-test when the flag asks for it; True if it ran.
     Called between Driver(...) and driver.startup(), so the first published
@@ -216,6 +238,9 @@ def startup_selftest(args, driver) -> bool:
     extra = {"per_cu": True} if args.selftest_per_cu == "on" else {}
     if args.selftest_load_seconds > 0:
         extra["load_seconds"] = args.selftest_load_seconds
+    formats = selftest_load_formats(args)
+    if formats:
+        extra["load_formats"] = formats
     driver.run_startup_selftest(
         mib=args.selftest_mib, timeout_s=args.selftest_timeout_s, **extra
     )
@@ -228,6 +253,7 @@ def main(argv=None) -> int:
 
     setup_logging(args.verbosity, json_format=args.logging_format == "json")
     require_selftest_extension(args)
+    selftest_load_formats(args)  # a bad flag stops the plugin before it starts
     lib = new_device_lib(args.hal)
     lib.open()
     kube = make_kube_client(args)

@@ -19,7 +19,10 @@ Two halves:
   CU it happened on. With ``--load-seconds S`` it goes on to
   ``_hiphealth.load_selftest``: a tiled bf16 MFMA GEMM on exact data runs for
   S seconds, every element of every iteration is compared bit for bit, and
-  the result goes under ``"load"``.
+  the result goes under ``"load"``. With ``--load-formats mxfp8,mxfp4`` each
+  named MX format then runs ``_hiphealth.mx_selftest`` (the same loop on the
+  block-scaled MFMA) for as long again, in the order given, and the results
+  go under ``"load_mx"``, one per format.
 - **parent** (:func:`run`): starts that child in a fresh process with a
   timeout, one child at a time, and turns what it says into a
   :class:`SelftestResult`. The calling process never initialises HIP, so a
@@ -48,6 +51,13 @@ DEFAULT_TIMEOUT_S = 120.0
 #: and its checksum on the host
 LOAD_GOLDEN_ALLOWANCE_S = 60.0
 MAX_LOAD_SECONDS = 600.0
+#: the MX formats the load stage can go on to, in the extension's order
+LOAD_FORMATS = ("mxfp8", "mxfp4")
+#: added to the child's time limit per MX format, on top of the load seconds:
+#: twice what mx_gemm_ref, the download and the host checksum take at 4096^3,
+#: measured as 0.25 s for mxfp8 and 0.19 s for mxfp4 on an MI355X
+#: (profiles/mx_selftest.md)
+MX_GOLDEN_ALLOWANCE_S = 0.5
 
 EXIT_PASS = 0
 EXIT_MISMATCH = 1
@@ -125,6 +135,14 @@ class SelftestResult:
         load = report.get("load") or {}
         if load and not load.get("ok", True):
             out.append(finding("SelftestComputeMismatch", _load_detail(load)))
+        for fmt, part in (report.get("load_mx") or {}).items():
+            if not part.get("ok", True):
+                out.append(
+                    finding(
+                        "SelftestComputeMismatch",
+                        f"{fmt} {_load_detail(part)}",
+                    )
+                )
         return out
 
 
@@ -194,24 +212,65 @@ def _load_detail(load: dict) -> str:
     return detail
 
 
-def _classify_load(load) -> bool:
+def parse_load_formats(text) -> Tuple[str, ...]:
+    """``"mxfp8,mxfp4"`` (or a sequence of names) as a tuple of format names
+    in the order given; raises ValueError on an unknown or repeated name."""
+    if isinstance(text, str):
+        names = [n.strip() for n in text.split(",") if n.strip()]
+    else:
+        names = [str(n) for n in (text or ())]
+    for name in names:
+        if name not in LOAD_FORMATS:
+            raise ValueError(
+                f"unknown load format {name!r} (known: {', '.join(LOAD_FORMATS)})"
+            )
+    if len(set(names)) != len(names):
+        raise ValueError("a load format is named twice")
+    return tuple(names)
+
+
+def _classify_load_mx(load_mx, formats) -> bool:
+    """True when an MX part of a report is bad; raises unless ``load_mx`` has
+    exactly the formats asked for, each with the documented shape of the
+    load part plus its own name. The child prints its report with sorted
+    keys, so the order the formats ran in is not in it: ``load_mx`` is put
+    back into the order asked for."""
+    if not isinstance(load_mx, dict):
+        raise TypeError("load_mx is not an object")
+    if sorted(load_mx) != sorted(formats):
+        raise ValueError(
+            f"load_mx has {sorted(load_mx)}, asked for {sorted(formats)}"
+        )
+    parts = {fmt: load_mx[fmt] for fmt in formats}
+    load_mx.clear()
+    load_mx.update(parts)
+    bad = False
+    for fmt, part in load_mx.items():
+        if not isinstance(part, dict) or part.get("format") != fmt:
+            raise ValueError(f"load_mx[{fmt!r}] does not carry its format")
+        if _classify_load(part, f"load_mx[{fmt!r}]"):
+            bad = True
+    return bad
+
+
+def _classify_load(load, name: str = "load") -> bool:
     """True when the load part of a report is bad (a mismatch or a failed
     checksum of the golden product); raises on a part that does not have the
     documented shape."""
     if not isinstance(load, dict):
-        raise TypeError("load is not an object")
+        raise TypeError(f"{name} is not an object")
     for key in ("m", "n", "k", "iterations", "mismatches", "cus_seen"):
         load[key] = int(load[key])
     if not isinstance(load["ok"], bool) or not isinstance(load["checksum_ok"], bool):
-        raise TypeError("load: ok and checksum_ok must be booleans")
+        raise TypeError(f"{name}: ok and checksum_ok must be booleans")
     load["checksum_first_bad"] = str(load.get("checksum_first_bad", ""))
     load["tflops"] = float(load["tflops"])
     load["records"] = [tuple(int(v) for v in r) for r in load["records"]]
     if any(len(r) != 5 for r in load["records"]):
-        raise ValueError("a record of load does not have 5 fields")
+        raise ValueError(f"a record of {name} does not have 5 fields")
     load["bad_tiles"] = [tuple(int(v) for v in t) for t in load["bad_tiles"]]
     if any(len(t) != 3 for t in load["bad_tiles"]):
-        raise ValueError("a bad tile of load does not have 3 fields")
+        raise ValueError(f"a bad tile of {name} does not have 3 fields")
     names = ("xcc", "se", "sh", "cu", "mismatches")
     load["bad_cus"] = [{k: int(c[k]) for k in names} for c in load["bad_cus"]]
     mismatched = bool(load["mismatches"])
@@ -222,10 +281,10 @@ def _classify_load(load) -> bool:
         or load["ok"] != (not mismatched and load["checksum_ok"])
     ):
         raise ValueError(
-            "load: ok, mismatches, checksum_ok and bad_cus disagree"
+            f"{name}: ok, mismatches, checksum_ok and bad_cus disagree"
         )
     if load["iterations"] < 1:
-        raise ValueError("load: no iteration ran")
+        raise ValueError(f"{name}: no iteration ran")
     return not load["ok"]
 
 
@@ -252,7 +311,7 @@ def _classify_cu(cu) -> bool:
     return bad
 
 
-def _classify(report: dict) -> str:
+def _classify(report: dict, load_formats=()) -> str:
     """pass | memory | compute from a child's report; raises on a report
     that does not have the documented shape."""
     memory_bad = any(int(p["mismatches"]) for p in report["memory"])
@@ -260,6 +319,8 @@ def _classify(report: dict) -> str:
     if "cu" in report and _classify_cu(report["cu"]):
         compute_bad = True
     if "load" in report and _classify_load(report["load"]):
+        compute_bad = True
+    if "load_mx" in report and _classify_load_mx(report["load_mx"], load_formats):
         compute_bad = True
     for part in list(report["memory"]) + [report["mfma"]]:
         part["records"] = [tuple(int(v) for v in r) for r in part["records"]]
@@ -308,15 +369,28 @@ def run(
     spawn: Spawn = _spawn_child,
     per_cu: bool = False,
     load_seconds: float = 0.0,
+    load_formats=(),
 ) -> SelftestResult:
     """Self-test one GPU (a ``hal.model.GpuInfo``: ``index`` and
     ``pcie_bdf`` are used) in a child process; ``per_cu`` adds the per-CU
     stage, a positive ``load_seconds`` the load stage of that length, which
     extends the child's time limit by as much plus
-    ``LOAD_GOLDEN_ALLOWANCE_S``. Never raises and never retries: whatever
-    goes wrong is an ``error`` result."""
+    ``LOAD_GOLDEN_ALLOWANCE_S``. Each MX format of ``load_formats`` (names of
+    ``LOAD_FORMATS``; only with a positive ``load_seconds``) then runs for
+    ``load_seconds`` as well and extends the limit by as much plus
+    ``MX_GOLDEN_ALLOWANCE_S``. Never raises and never retries: whatever goes
+    wrong is an ``error`` result."""
     bdf = gpu.pcie_bdf
     load_seconds = float(load_seconds)
+    t0 = time.monotonic()
+    try:
+        load_formats = parse_load_formats(load_formats)
+        if load_formats and not load_seconds > 0:
+            raise ValueError("load formats need a positive load_seconds")
+    except ValueError as e:
+        return SelftestResult(
+            gpu_index=gpu.index, bdf=bdf, outcome="error", error=str(e)
+        )
     argv = [
         sys.executable,
         "-m",
@@ -333,6 +407,9 @@ def run(
     if with_load:
         argv += ["--load-seconds", f"{load_seconds:g}"]
         timeout_s = timeout_s + load_seconds + LOAD_GOLDEN_ALLOWANCE_S
+    if load_formats:
+        argv += ["--load-formats", ",".join(load_formats)]
+        timeout_s += len(load_formats) * (load_seconds + MX_GOLDEN_ALLOWANCE_S)
 
     def result(outcome, report=None, error=""):
         return SelftestResult(
@@ -375,7 +452,11 @@ def run(
                 raise KeyError("cu")
             if with_load and "load" not in report:
                 raise KeyError("load")
-            outcome = _classify(report)
+            if load_formats and "load_mx" not in report:
+                raise KeyError("load_mx")
+            if not load_formats and "load_mx" in report:
+                raise ValueError("load_mx was not asked for")
+            outcome = _classify(report, load_formats)
         except (KeyError, TypeError, ValueError) as e:
             return result("error", error=f"exit {rc}, malformed report: {e!r}")
         if (outcome == "pass") != (rc == EXIT_PASS):
@@ -389,7 +470,11 @@ def run(
 # child
 # ---------------------------------------------------------------------------
 def _child(
-    bdf: str, mib: int, per_cu: bool = False, load_seconds: float = 0.0
+    bdf: str,
+    mib: int,
+    per_cu: bool = False,
+    load_seconds: float = 0.0,
+    load_formats=(),
 ) -> Tuple[int, dict]:
     try:
         from k8s_dra_driver_amd import _hiphealth
@@ -410,6 +495,12 @@ def _child(
                         ordinal, seconds=load_seconds
                     )
                     report["ok"] = bool(report["ok"] and report["load"]["ok"])
+                if load_formats:
+                    report["load_mx"] = {}
+                    for fmt in load_formats:
+                        part = _hiphealth.mx_selftest(ordinal, fmt, load_seconds)
+                        report["load_mx"][fmt] = part
+                        report["ok"] = bool(report["ok"] and part["ok"])
                 return (EXIT_PASS if report["ok"] else EXIT_MISMATCH), report
         return EXIT_ERROR, {
             "ok": False,
@@ -438,12 +529,28 @@ def main(argv=None) -> int:
         help="also run the load test (a tiled bf16 GEMM on exact data, "
         "every element of every iteration compared) for this long; 0 = off",
     )
+    ap.add_argument(
+        "--load-formats",
+        default="",
+        help="after the load test, run it again on the block-scaled MFMA for "
+        "each of these MX formats (comma-separated: "
+        + ", ".join(LOAD_FORMATS)
+        + "), --load-seconds each; needs --load-seconds",
+    )
     ap.add_argument("--json", action="store_true", help="print the full report")
     args = ap.parse_args(argv)
     t0 = time.monotonic()
     if args.load_seconds < 0 or args.load_seconds > MAX_LOAD_SECONDS:
         ap.error(f"--load-seconds must be in [0, {MAX_LOAD_SECONDS:g}]")
+    try:
+        formats = parse_load_formats(args.load_formats)
+    except ValueError as e:
+        ap.error(f"--load-formats: {e}")
+    if formats and not args.load_seconds > 0:
+        ap.error("--load-formats needs a positive --load-seconds")
     extra = {"load_seconds": args.load_seconds} if args.load_seconds > 0 else {}
+    if formats:
+        extra["load_formats"] = formats
     rc, report = _child(args.bdf, args.mib, args.per_cu, **extra)
     report["seconds"] = round(time.monotonic() - t0, 3)
     if args.json:
@@ -475,6 +582,15 @@ def main(argv=None) -> int:
                 f"{load['mismatches']} mismatch(es), checksum "
                 f"{'ok' if load['checksum_ok'] else 'FAILED'}; "
                 f"{load['tflops']:.0f} TF/s (informative)"
+            )
+        for fmt, part in report.get("load_mx", {}).items():
+            print(
+                f"{args.bdf}: load {fmt}: {part['iterations']} iteration(s) of "
+                f"{part['m']}x{part['n']}x{part['k']} in "
+                f"{part['seconds']:.1f}s on {part['cus_seen']} CUs, "
+                f"{part['mismatches']} mismatch(es), checksum "
+                f"{'ok' if part['checksum_ok'] else 'FAILED'}; "
+                f"{part['tflops']:.0f} TF/s (informative)"
             )
     return rc
 

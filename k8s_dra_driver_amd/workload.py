@@ -185,6 +185,16 @@ def main(argv=None) -> int:
         "bit and name the tiles and CUs that fail; exit 1 on a mismatch",
     )
     ap.add_argument(
+        "--mx-selftest",
+        nargs=2,
+        default=None,
+        metavar=("FORMAT", "SECONDS"),
+        help="run a tiled GEMM on the block-scaled MFMA (FORMAT mxfp8 or "
+        "mxfp4) on exact data on every visible device for SECONDS, compare "
+        "every element of every iteration bit for bit and name the tiles and "
+        "CUs that fail; exit 1 on a mismatch",
+    )
+    ap.add_argument(
         "--cu-footprint",
         action="store_true",
         help="print which compute units this process's blocks run on, per "
@@ -192,6 +202,20 @@ def main(argv=None) -> int:
         "exit 1 if a device shows more CUs than its mask allows",
     )
     args = ap.parse_args(argv)
+    mx = None
+    if args.mx_selftest:
+        from k8s_dra_driver_amd.selftest import LOAD_FORMATS, MAX_LOAD_SECONDS
+
+        fmt, seconds = args.mx_selftest
+        if fmt not in LOAD_FORMATS:
+            ap.error(f"--mx-selftest: FORMAT must be one of {', '.join(LOAD_FORMATS)}")
+        try:
+            seconds = float(seconds)
+        except ValueError:
+            ap.error("--mx-selftest: SECONDS must be a number")
+        if not 0 < seconds <= MAX_LOAD_SECONDS:
+            ap.error(f"--mx-selftest: SECONDS must be in (0, {MAX_LOAD_SECONDS:g}]")
+        mx = (fmt, seconds)
 
     info = visible_devices()
     print(json.dumps(info))
@@ -206,6 +230,7 @@ def main(argv=None) -> int:
         or args.selftest
         or args.cu_selftest
         or args.load_selftest
+        or mx
         or args.cu_footprint
     ):
         from k8s_dra_driver_amd import _hiphealth
@@ -263,6 +288,24 @@ def main(argv=None) -> int:
                 )
                 print(
                     f"device {d}: load-selftest {'ok' if r['ok'] else 'FAILED'}: "
+                    f"{r['iterations']} iteration(s) of "
+                    f"{r['m']}x{r['n']}x{r['k']} in {r['seconds']:.1f}s on "
+                    f"{r['cus_seen']} CUs, {r['mismatches']} mismatch(es), "
+                    f"checksum {'ok' if r['checksum_ok'] else 'FAILED'}, "
+                    f"{r['tflops']:.0f} TF/s (informative), "
+                    f"{len(r['bad_cus'])} bad CU(s)" + (f": {bad}" if bad else "")
+                )
+                if not r["ok"]:
+                    rc = 1
+            if mx:
+                r = _hiphealth.mx_selftest(d, mx[0], mx[1])
+                bad = ", ".join(
+                    f"xcc {c['xcc']} se {c['se']} sh {c['sh']} cu {c['cu']}"
+                    for c in r["bad_cus"]
+                )
+                print(
+                    f"device {d}: mx-selftest {mx[0]} "
+                    f"{'ok' if r['ok'] else 'FAILED'}: "
                     f"{r['iterations']} iteration(s) of "
                     f"{r['m']}x{r['n']}x{r['k']} in {r['seconds']:.1f}s on "
                     f"{r['cus_seen']} CUs, {r['mismatches']} mismatch(es), "
