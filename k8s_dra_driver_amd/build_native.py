@@ -100,7 +100,7 @@ def build_amdhal_asan(force: bool = False) -> str:
 def build_hiphealth(force: bool = False) -> str:
     """HIP kernels; rebuilt when the source or a header it includes (the
     self-test's, the CU footprint's, the per-CU self-test's, the load
-    self-test's, the MX load self-test's) changes."""
+    self-test's, the MX load self-test's, the HBM march's) changes."""
     src = os.path.join(CPP_DIR, "hiphealth.hip")
     hdrs = [
         os.path.join(CPP_DIR, "selftest_kernels.hpp"),
@@ -110,6 +110,8 @@ def build_hiphealth(force: bool = False) -> str:
         os.path.join(CPP_DIR, "loadtest_core.hpp"),
         os.path.join(CPP_DIR, "mxtest_kernels.hpp"),
         os.path.join(CPP_DIR, "mxtest_core.hpp"),
+        os.path.join(CPP_DIR, "hbmtest_kernels.hpp"),
+        os.path.join(CPP_DIR, "hbmtest_core.hpp"),
     ]
     out = os.path.join(PKG_DIR, f"_hiphealth{_ext_suffix()}")
     if force or _needs_build(src, out) or any(_needs_build(h, out) for h in hdrs):
@@ -218,6 +220,26 @@ def build_mxtest_core_selftest(out: str, sanitize: bool = True) -> str:
     ``main``, no Python, no HIP), by default under AddressSanitizer + UBSan.
     CPU only; run the binary directly."""
     src = os.path.join(CPP_DIR, "mxtest_core_selftest.cpp")
+    flags = ["-g", "-O1", "-std=c++17"]
+    if sanitize:
+        link = sanitizer_link_flags()
+        if link is None:
+            raise RuntimeError("gcc has no ASan/UBSan runtime installed")
+        flags += [
+            "-fsanitize=address,undefined",
+            "-fno-sanitize-recover=undefined",
+            "-fno-omit-frame-pointer",
+        ] + link
+    _run(["g++"] + flags + [src, "-o", out])
+    return out
+
+
+def build_hbmtest_core_selftest(out: str, sanitize: bool = True) -> str:
+    """Stand-alone driver of hbmtest_core.hpp (the HBM march's chunk plan,
+    round schedule, expected word and report aggregation; its own ``main``,
+    no Python, no HIP), by default under AddressSanitizer + UBSan. CPU only;
+    run the binary directly."""
+    src = os.path.join(CPP_DIR, "hbmtest_core_selftest.cpp")
     flags = ["-g", "-O1", "-std=c++17"]
     if sanitize:
         link = sanitizer_link_flags()

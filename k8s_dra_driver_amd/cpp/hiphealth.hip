@@ -28,6 +28,9 @@
 //   mx_selftest()    - the same on the block-scaled MFMA
 //                      (v_mfma_scale_f32_16x16x128_f8f6f4) with mxfp8 or
 //                      mxfp4 operands and E8M0 scales (mxtest_kernels.hpp)
+//   hbm_selftest()   - HBM march: all free memory in 1 GiB chunks, every
+//                      element read, verified and rewritten in place, pass
+//                      after pass for a time budget (hbmtest_kernels.hpp)
 //
 // Written for gfx950: 64-wide waves, 256 CUs in 8 XCDs (grids sized
 // >> 256 workgroups), 16 B/lane streaming accesses.
@@ -43,9 +46,12 @@
 #include <cstdint>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 namespace py = pybind11;
@@ -684,6 +690,11 @@ py::bytes mfma_burn_probe(int device, int iters, int blocks) {
 #include "mxtest_kernels.hpp"
 
 // ---------------------------------------------------------------------------
+// HBM march: all free memory, read-verify-write in place under load
+// ---------------------------------------------------------------------------
+#include "hbmtest_kernels.hpp"
+
+// ---------------------------------------------------------------------------
 // device info
 // ---------------------------------------------------------------------------
 int device_count() {
@@ -906,4 +917,42 @@ PYBIND11_MODULE(_hiphealth, m) {
         "map. The scales travel in byte opsel of the scale registers, whose "
         "other bytes hold other_scale. Returns guard + D[16][16] float32 + "
         "guard");
+  m.attr("HBMTEST_CHUNK_BYTES") = kHbChunkBytes;
+  m.attr("HBMTEST_PAGE_BYTES") = kHbPageBytes;
+  m.attr("HBMTEST_MIN_BYTES") = kHbMinBytes;
+  m.attr("HBMTEST_RESERVE_MIN_BYTES") = kHbReserveMinBytes;
+  m.attr("HBMTEST_RESERVE_PERCENT") = kHbReservePercent;
+  m.def("hbm_selftest", &hbm_selftest, py::arg("device") = 0,
+        py::arg("seconds") = 5.0, py::arg("mib") = 0,
+        py::arg("seed") = 0x5E1F7E57C0FFEEull, py::arg("blocks") = 0,
+        "HBM march: mib MiB (0 = what hipMemGetInfo reports free less "
+        "max(HBMTEST_RESERVE_MIN_BYTES, HBMTEST_RESERVE_PERCENT % of the "
+        "total), rounded down to HBMTEST_PAGE_BYTES) are allocated as chunks "
+        "of HBMTEST_CHUNK_BYTES; an allocation the device has no room for "
+        "ends the allocating (alloc_short), and less than HBMTEST_MIN_BYTES "
+        "in all is an error. Global word w of the coverage holds pattern r % "
+        "4 of (addr, addr_inv, hash, hash_inv) with seed mix(seed + r / 4) "
+        "after round r. Pass 0 fills round 0, pass p reads and compares "
+        "round p - 1 and writes round p to the same element, the last pass "
+        "only reads; every pass covers every chunk before the next starts "
+        "(grid=blocks, 0 = 1024), odd cycles of four go from the top down, "
+        "and passes run until seconds (in (0, 600]) have passed, to the end "
+        "of a cycle. A pass with a mismatch is the last. Returns {ok, device, "
+        "seed, seconds, alloc_seconds, bytes, chunks, chunk_bytes: [bytes], "
+        "free_bytes, total_bytes, alloc_short, rounds, passes, mismatches, "
+        "flipped_or, bad_chunks: [(chunk, mismatches)], bad_pages, "
+        "bad_pages_first: [(chunk, page)], records: [(pass, word, got, "
+        "want)], gbs: {fill, march_addr, march_hash, verify}}; gbs is "
+        "event-timed, counts read + write for the march passes and is "
+        "informative only");
+  m.def("hbm_march_probe", &hbm_march_probe, py::arg("device"),
+        py::arg("nbytes"), py::arg("seed"), py::arg("rounds"),
+        py::arg("blocks"), py::arg("chunk_bytes"), py::arg("flips"),
+        "The HBM march's host loop and kernels on nbytes (a multiple of 16, "
+        "at most 64 MiB) in guarded chunks of chunk_bytes (a multiple of 16, "
+        "at most 64 chunks) for exactly `rounds` rounds with grid=blocks. "
+        "Every (pass, global word, mask) of flips, 1 <= pass <= rounds, is "
+        "XORed in after pass - 1 has written and before pass reads; all of "
+        "them are checked before the first launch. Returns ([guard + chunk + "
+        "guard], the dict of hbm_selftest)");
 }

@@ -14,6 +14,7 @@ projection, carve/restore partitions, and run the health probes.
     amd-dra-ctl health --selftest --per-cu   # + LDS / MFMA test of every CU
     amd-dra-ctl health --selftest --load-seconds 5   # + checked GEMM under load
     amd-dra-ctl health --selftest --load-seconds 5 --load-formats mxfp8,mxfp4
+    amd-dra-ctl health --selftest --hbm-seconds 10   # + march over all free HBM
                                      # + the same on the block-scaled MFMA
 Use ``--hal fake`` anywhere to drive the modeled 8xMI355X node.
 """
@@ -211,6 +212,8 @@ def _selftest_into(
     per_cu: bool = False,
     load_seconds: float = 0.0,
     load_formats=(),
+    hbm_seconds: float = 0.0,
+    hbm_mib: int = 0,
 ) -> None:
     """Self-test one GPU in a child process and add what it found to the
     GPU's record. The operator vouches that nothing is using the GPU; a
@@ -225,6 +228,10 @@ def _selftest_into(
         extra["load_seconds"] = load_seconds
     if load_formats:
         extra["load_formats"] = tuple(load_formats)
+    if hbm_seconds > 0:
+        extra["hbm_seconds"] = hbm_seconds
+        if hbm_mib:
+            extra["hbm_mib"] = hbm_mib
     res = selftest.run(g, mib=mib, **extra)
     rec["selftest"] = {
         "result": res.outcome,
@@ -261,6 +268,19 @@ def _selftest_into(
             }
             for fmt, part in load_mx.items()
         }
+    hbm = (res.report or {}).get("hbm") if hbm_seconds > 0 else None
+    if hbm:
+        rec["selftest"]["hbm"] = {
+            "bytes": hbm["bytes"],
+            "chunks": hbm["chunks"],
+            "alloc_short": hbm["alloc_short"],
+            "passes": hbm["passes"],
+            "mismatches": hbm["mismatches"],
+            "flipped_or": hbm["flipped_or"],
+            "bad_chunks": hbm["bad_chunks"],
+            "bad_pages": hbm["bad_pages"],
+            "gbs": hbm["gbs"],
+        }
     rec["findings"] += [
         {"reason": f.reason, "severity": f.severity, "detail": f.detail}
         for f in res.findings()
@@ -281,6 +301,8 @@ def cmd_health(args) -> int:
                 args.per_cu,
                 args.load_seconds,
                 args.load_formats,
+                args.hbm_seconds,
+                args.hbm_mib,
             )
         records.append(rec)
         if not args.json:
@@ -321,6 +343,15 @@ def cmd_health(args) -> int:
                         f"{'ok' if part['checksum_ok'] else 'FAILED'}, "
                         f"{part['cus_seen']} CUs seen, "
                         f"{part['tflops']:.0f} TF/s (informative)"
+                    )
+                if "hbm" in st:
+                    hbm = st["hbm"]
+                    print(
+                        f"    hbm march: {hbm['passes']} pass(es) over "
+                        f"{hbm['bytes'] / 2**30:.1f} GiB in {hbm['chunks']} "
+                        f"chunk(s), {hbm['mismatches']} mismatch(es) in "
+                        f"{hbm['bad_pages']} 2 MiB block(s), march "
+                        f"{hbm['gbs']['march_hash']:.0f} GB/s (informative)"
                     )
                 if not args.signals:
                     for f in rec["findings"]:
@@ -441,6 +472,21 @@ def main(argv=None) -> int:
         "--load-seconds each",
     )
     hp.add_argument(
+        "--hbm-seconds",
+        type=float,
+        default=0.0,
+        help="with --selftest, finish with the HBM march: all free memory "
+        "is written, then read, verified and rewritten in place, pass after "
+        "pass, for this many seconds per GPU (0 = off)",
+    )
+    hp.add_argument(
+        "--hbm-mib",
+        type=int,
+        default=0,
+        help="with --hbm-seconds, the memory the march covers, at least "
+        "1024 (0 = all that is free less max(2 GiB, 2 %% of the total))",
+    )
+    hp.add_argument(
         "--selftest-mib",
         type=int,
         default=1024,
@@ -458,6 +504,17 @@ def main(argv=None) -> int:
         args.selftest and args.load_seconds > 0
     ):
         ap.error("--load-formats needs --selftest and a positive --load-seconds")
+    if args.cmd == "health":
+        from .selftest import HBM_MIN_BYTES, MAX_LOAD_SECONDS
+
+        if not 0 <= args.hbm_seconds <= MAX_LOAD_SECONDS:
+            ap.error(f"--hbm-seconds must be in [0, {MAX_LOAD_SECONDS:g}]")
+        if args.hbm_seconds > 0 and not args.selftest:
+            ap.error("--hbm-seconds needs --selftest")
+        if args.hbm_mib and not args.hbm_seconds > 0:
+            ap.error("--hbm-mib needs a positive --hbm-seconds")
+        if args.hbm_mib < 0 or 0 < args.hbm_mib < HBM_MIN_BYTES >> 20:
+            ap.error("--hbm-mib must be 0 or at least 1024")
     return {
         "list": cmd_list,
         "topology": cmd_topology,

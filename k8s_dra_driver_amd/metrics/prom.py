@@ -180,6 +180,25 @@ class PluginMetrics:
             ["gpu", "format"],
             registry=self.registry,
         )
+        # its HBM march, set only when that stage ran
+        self.gpu_selftest_hbm_bytes = Gauge(
+            "dra_gpu_selftest_hbm_bytes",
+            "Bytes of HBM the last startup HBM march covered",
+            ["gpu"],
+            registry=self.registry,
+        )
+        self.gpu_selftest_hbm_passes = Gauge(
+            "dra_gpu_selftest_hbm_passes",
+            "Passes over its whole coverage the last startup HBM march ran",
+            ["gpu"],
+            registry=self.registry,
+        )
+        self.gpu_selftest_hbm_mismatches = Gauge(
+            "dra_gpu_selftest_hbm_mismatches",
+            "Mismatching 64-bit words in the last startup HBM march",
+            ["gpu"],
+            registry=self.registry,
+        )
         #: gpu label -> reason label currently exported as dra_gpu_unhealthy
         self._unhealthy_reason = {}
 

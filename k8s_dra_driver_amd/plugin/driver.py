@@ -229,6 +229,8 @@ class Driver:
         per_cu: bool = False,
         load_seconds: float = 0,
         load_formats=(),
+        hbm_seconds: float = 0,
+        hbm_mib: int = 0,
     ) -> Dict[int, str]:
         """Self-test every GPU in scope that nothing is using, one after
         another, and hand the findings to the health monitor. Meant for
@@ -243,7 +245,11 @@ class Driver:
         with ``load_seconds``. A non-empty ``load_formats`` (MX format
         names, e.g. ``("mxfp8", "mxfp4")``) runs the load stage again on the
         block-scaled MFMA for each of them; only then is the runner called
-        with ``load_formats``.
+        with ``load_formats``. A positive ``hbm_seconds`` adds the HBM march
+        as the last stage (all free memory less a reserve, or ``hbm_mib``
+        MiB, read, verified and rewritten in place for that long); only then
+        is the runner called with ``hbm_seconds``, and with ``hbm_mib`` only
+        when that is not 0.
 
         A GPU is skipped (logged, no finding) when a claim recovered from
         the checkpoints holds it, when it is partitioned, or when it has
@@ -277,7 +283,11 @@ class Driver:
                 extra["load_seconds"] = load_seconds
             if load_formats:
                 extra["load_formats"] = tuple(load_formats)
-            cu = load = load_mx = None
+            if hbm_seconds and hbm_seconds > 0:
+                extra["hbm_seconds"] = hbm_seconds
+                if hbm_mib:
+                    extra["hbm_mib"] = hbm_mib
+            cu = load = load_mx = hbm = None
             try:
                 res = runner(gpu, mib=mib, timeout_s=timeout_s, **extra)
                 outcome, findings = res.outcome, res.findings()
@@ -287,6 +297,8 @@ class Driver:
                     load = (res.report or {}).get("load")
                 if "load_formats" in extra:
                     load_mx = (res.report or {}).get("load_mx")
+                if "hbm_seconds" in extra:
+                    hbm = (res.report or {}).get("hbm")
             except Exception as e:
                 log.exception("gpu-%d: startup self-test failed to run", idx)
                 from .health import HealthFinding, SOFT
@@ -317,6 +329,14 @@ class Driver:
                 )
                 self.metrics.gpu_selftest_mx_mismatches.labels(str(idx), fmt).set(
                     part["mismatches"]
+                )
+            if hbm:
+                self.metrics.gpu_selftest_hbm_bytes.labels(str(idx)).set(hbm["bytes"])
+                self.metrics.gpu_selftest_hbm_passes.labels(str(idx)).set(
+                    hbm["passes"]
+                )
+                self.metrics.gpu_selftest_hbm_mismatches.labels(str(idx)).set(
+                    hbm["mismatches"]
                 )
             self.health.set_selftest_findings(idx, findings)
             if findings:

@@ -171,6 +171,22 @@ def build_parser() -> argparse.ArgumentParser:
         "--selftest-timeout-s (empty = off)",
     )
     p.add_argument(
+        "--selftest-hbm-seconds",
+        type=float,
+        default=float(_env("SELFTEST_HBM_SECONDS", "0")),
+        help="with --startup-selftest on, finish with the HBM march: all "
+        "free memory of the GPU is written, then read, verified and "
+        "rewritten in place, pass after pass, for this many seconds (0 = "
+        "off, at most 600); the time is added to --selftest-timeout-s",
+    )
+    p.add_argument(
+        "--selftest-hbm-mib",
+        type=int,
+        default=int(_env("SELFTEST_HBM_MIB", "0")),
+        help="memory the HBM march covers per GPU, at least 1024 (0 = all "
+        "that is free less max(2 GiB, 2 %% of the total))",
+    )
+    p.add_argument(
         "--selftest-timeout-s",
         type=float,
         default=float(_env("SELFTEST_TIMEOUT_S", "120")),
@@ -229,6 +245,29 @@ def selftest_load_formats(args) -> tuple:
     return formats
 
 
+def selftest_hbm(args) -> dict:
+    """--selftest-hbm-seconds and --selftest-hbm-mib as the keyword arguments
+    they add to the self-test ({} when the march is off); raises ValueError
+    on seconds outside [0, MAX_LOAD_SECONDS], on a coverage below 1 GiB, or
+    on a coverage without seconds."""
+    from .. import selftest
+
+    seconds, mib = args.selftest_hbm_seconds, args.selftest_hbm_mib
+    if not 0 <= seconds <= selftest.MAX_LOAD_SECONDS:
+        raise ValueError(
+            f"--selftest-hbm-seconds must be in [0, {selftest.MAX_LOAD_SECONDS:g}]"
+        )
+    if mib < 0 or 0 < mib < selftest.HBM_MIN_BYTES >> 20:
+        raise ValueError("--selftest-hbm-mib must be 0 or at least 1024")
+    if mib and not seconds > 0:
+        raise ValueError(
+            "--selftest-hbm-mib needs a positive --selftest-hbm-seconds"
+        )
+    if not seconds > 0:
+        return {}
+    return {"hbm_seconds": seconds, "hbm_mib": mib} if mib else {"hbm_seconds": seconds}
+
+
 def startup_selftest(args, driver) -> bool:
     """Run the startup self-test when the flag asks for it; True if it ran.
     Called between Driver(...) and driver.startup(), so the first published
@@ -241,6 +280,7 @@ def startup_selftest(args, driver) -> bool:
     formats = selftest_load_formats(args)
     if formats:
         extra["load_formats"] = formats
+    extra.update(selftest_hbm(args))
     driver.run_startup_selftest(
         mib=args.selftest_mib, timeout_s=args.selftest_timeout_s, **extra
     )
@@ -254,6 +294,7 @@ def main(argv=None) -> int:
     setup_logging(args.verbosity, json_format=args.logging_format == "json")
     require_selftest_extension(args)
     selftest_load_formats(args)  # a bad flag stops the plugin before it starts
+    selftest_hbm(args)
     lib = new_device_lib(args.hal)
     lib.open()
     kube = make_kube_client(args)

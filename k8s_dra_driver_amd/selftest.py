@@ -22,7 +22,11 @@ Two halves:
   the result goes under ``"load"``. With ``--load-formats mxfp8,mxfp4`` each
   named MX format then runs ``_hiphealth.mx_selftest`` (the same loop on the
   block-scaled MFMA) for as long again, in the order given, and the results
-  go under ``"load_mx"``, one per format.
+  go under ``"load_mx"``, one per format. With ``--hbm-seconds S`` the last
+  stage is ``_hiphealth.hbm_selftest``, the HBM march: all free memory less a
+  reserve (or ``--hbm-mib N``) is written, then read, verified and rewritten
+  in place pass after pass for S seconds, and the result goes under
+  ``"hbm"``.
 - **parent** (:func:`run`): starts that child in a fresh process with a
   timeout, one child at a time, and turns what it says into a
   :class:`SelftestResult`. The calling process never initialises HIP, so a
@@ -58,6 +62,17 @@ LOAD_FORMATS = ("mxfp8", "mxfp4")
 #: measured as 0.25 s for mxfp8 and 0.19 s for mxfp4 on an MI355X
 #: (profiles/mx_selftest.md)
 MX_GOLDEN_ALLOWANCE_S = 0.5
+#: added to the child's time limit with the HBM march, on top of its seconds:
+#: twice what allocating 282 chunks (7.0 s), the first five passes (the
+#: shortest run there is, 0.5 s) and freeing the chunks (2.5 s) were measured
+#: to take at the default coverage of an empty MI355X, 302 GB
+#: (profiles/hbm_selftest.md)
+HBM_ALLOWANCE_S = 20.0
+#: the least the HBM march covers: below it the region would sit in the
+#: 256 MiB Infinity Cache
+HBM_MIN_BYTES = 1 << 30
+#: how many bad 2 MiB blocks a finding spells out
+MAX_PAGES_IN_DETAIL = 4
 
 EXIT_PASS = 0
 EXIT_MISMATCH = 1
@@ -143,6 +158,9 @@ class SelftestResult:
                         f"{fmt} {_load_detail(part)}",
                     )
                 )
+        hbm = report.get("hbm") or {}
+        if hbm and not hbm.get("ok", True):
+            out.append(finding("SelftestMemoryMismatch", _hbm_detail(hbm)))
         return out
 
 
@@ -208,6 +226,31 @@ def _load_detail(load: dict) -> str:
         detail += (
             f"; first recorded value: iteration {it} row {row} col {col}: "
             f"got 0x{got:08x}, want 0x{want:08x}"
+        )
+    return detail
+
+
+def _hbm_detail(hbm: dict) -> str:
+    """The HBM march's part of a report as one finding's text: how many words
+    were wrong in how many passes over how much memory, which bits flipped,
+    the first few bad 2 MiB blocks by (chunk, block) and the lowest record."""
+    detail = (
+        f"hbm march: {hbm['mismatches']} mismatching word(s) in "
+        f"{hbm['passes']} pass(es) over {hbm['bytes'] / 2**30:.1f} GiB; "
+        f"flipped bits 0x{hbm['flipped_or']:016x}; "
+        f"{hbm['bad_pages']} bad 2 MiB block(s): "
+    )
+    first = hbm["bad_pages_first"]
+    detail += ", ".join(
+        f"chunk {c} block {p}" for c, p in first[:MAX_PAGES_IN_DETAIL]
+    )
+    if hbm["bad_pages"] > MAX_PAGES_IN_DETAIL:
+        detail += f", and {hbm['bad_pages'] - MAX_PAGES_IN_DETAIL} more"
+    if hbm["records"]:
+        p, word, got, want = min(hbm["records"])
+        detail += (
+            f"; first recorded word: pass {p} word {word}: "
+            f"got 0x{got:016x}, want 0x{want:016x}"
         )
     return detail
 
@@ -288,6 +331,62 @@ def _classify_load(load, name: str = "load") -> bool:
     return not load["ok"]
 
 
+def _classify_hbm(hbm) -> bool:
+    """True when the HBM march's part of a report lists a mismatch; raises on
+    a part that does not have the documented shape, that contradicts itself,
+    or that covered too little to have tested HBM."""
+    if not isinstance(hbm, dict):
+        raise TypeError("hbm is not an object")
+    for key in (
+        "bytes", "chunks", "free_bytes", "total_bytes", "rounds", "passes",
+        "mismatches", "flipped_or", "bad_pages",
+    ):
+        if isinstance(hbm[key], (bool, float)):
+            raise TypeError(f"hbm: {key} must be an integer")
+        hbm[key] = int(hbm[key])
+        if hbm[key] < 0:
+            raise ValueError(f"hbm: {key} is negative")
+    if not isinstance(hbm["ok"], bool) or not isinstance(hbm["alloc_short"], bool):
+        raise TypeError("hbm: ok and alloc_short must be booleans")
+    hbm["seconds"] = float(hbm["seconds"])
+    hbm["chunk_bytes"] = [int(b) for b in hbm["chunk_bytes"]]
+    hbm["gbs"] = {str(k): float(v) for k, v in dict(hbm["gbs"]).items()}
+    hbm["records"] = [tuple(int(v) for v in r) for r in hbm["records"]]
+    if any(len(r) != 4 for r in hbm["records"]):
+        raise ValueError("a record of hbm does not have 4 fields")
+    hbm["bad_chunks"] = [tuple(int(v) for v in c) for c in hbm["bad_chunks"]]
+    if any(len(c) != 2 for c in hbm["bad_chunks"]):
+        raise ValueError("a bad chunk of hbm does not have 2 fields")
+    hbm["bad_pages_first"] = [
+        tuple(int(v) for v in p) for p in hbm["bad_pages_first"]
+    ]
+    if any(len(p) != 2 for p in hbm["bad_pages_first"]):
+        raise ValueError("a bad page of hbm does not have 2 fields")
+    mismatched = bool(hbm["mismatches"])
+    if (
+        mismatched != bool(hbm["records"])
+        or mismatched != bool(hbm["bad_chunks"])
+        or mismatched != bool(hbm["bad_pages"])
+        or mismatched != bool(hbm["bad_pages_first"])
+        or mismatched != bool(hbm["flipped_or"])
+        or hbm["ok"] == mismatched
+    ):
+        raise ValueError(
+            "hbm: ok, mismatches, records, bad_chunks and bad_pages disagree"
+        )
+    if sum(n for _, n in hbm["bad_chunks"]) != hbm["mismatches"]:
+        raise ValueError("hbm: bad_chunks do not add up to mismatches")
+    if len(hbm["chunk_bytes"]) != hbm["chunks"] or sum(hbm["chunk_bytes"]) != hbm["bytes"]:
+        raise ValueError("hbm: chunk_bytes do not add up to bytes")
+    if hbm["bytes"] < HBM_MIN_BYTES:
+        raise ValueError(f"hbm: {hbm['bytes']} bytes covered, less than 1 GiB")
+    # a clean run is a fill, at least one cycle of four rounds and a verify;
+    # a run that found something may have stopped at any pass that reads
+    if hbm["passes"] < (2 if mismatched else 5):
+        raise ValueError(f"hbm: only {hbm['passes']} pass(es) ran")
+    return mismatched
+
+
 def _classify_cu(cu) -> bool:
     """True when the per-CU part of a report lists a mismatch; raises on a
     part that does not have the documented shape."""
@@ -322,6 +421,8 @@ def _classify(report: dict, load_formats=()) -> str:
         compute_bad = True
     if "load_mx" in report and _classify_load_mx(report["load_mx"], load_formats):
         compute_bad = True
+    if "hbm" in report and _classify_hbm(report["hbm"]):
+        memory_bad = True
     for part in list(report["memory"]) + [report["mfma"]]:
         part["records"] = [tuple(int(v) for v in r) for r in part["records"]]
     if any("pattern" not in p for p in report["memory"]):
@@ -370,6 +471,8 @@ def run(
     per_cu: bool = False,
     load_seconds: float = 0.0,
     load_formats=(),
+    hbm_seconds: float = 0.0,
+    hbm_mib: int = 0,
 ) -> SelftestResult:
     """Self-test one GPU (a ``hal.model.GpuInfo``: ``index`` and
     ``pcie_bdf`` are used) in a child process; ``per_cu`` adds the per-CU
@@ -378,15 +481,24 @@ def run(
     ``LOAD_GOLDEN_ALLOWANCE_S``. Each MX format of ``load_formats`` (names of
     ``LOAD_FORMATS``; only with a positive ``load_seconds``) then runs for
     ``load_seconds`` as well and extends the limit by as much plus
-    ``MX_GOLDEN_ALLOWANCE_S``. Never raises and never retries: whatever goes
+    ``MX_GOLDEN_ALLOWANCE_S``. A positive ``hbm_seconds`` adds the HBM march
+    of that length as the last stage, over ``hbm_mib`` MiB (0 = all free
+    memory less the reserve), and extends the limit by as much plus
+    ``HBM_ALLOWANCE_S``. Never raises and never retries: whatever goes
     wrong is an ``error`` result."""
     bdf = gpu.pcie_bdf
     load_seconds = float(load_seconds)
+    hbm_seconds = float(hbm_seconds)
     t0 = time.monotonic()
     try:
         load_formats = parse_load_formats(load_formats)
         if load_formats and not load_seconds > 0:
             raise ValueError("load formats need a positive load_seconds")
+        hbm_mib = int(hbm_mib)
+        if hbm_mib and not hbm_seconds > 0:
+            raise ValueError("hbm_mib needs a positive hbm_seconds")
+        if hbm_mib < 0 or 0 < hbm_mib < HBM_MIN_BYTES >> 20:
+            raise ValueError("hbm_mib must be 0 or at least 1024")
     except ValueError as e:
         return SelftestResult(
             gpu_index=gpu.index, bdf=bdf, outcome="error", error=str(e)
@@ -410,6 +522,12 @@ def run(
     if load_formats:
         argv += ["--load-formats", ",".join(load_formats)]
         timeout_s += len(load_formats) * (load_seconds + MX_GOLDEN_ALLOWANCE_S)
+    with_hbm = hbm_seconds > 0
+    if with_hbm:
+        argv += ["--hbm-seconds", f"{hbm_seconds:g}"]
+        if hbm_mib:
+            argv += ["--hbm-mib", str(hbm_mib)]
+        timeout_s = timeout_s + hbm_seconds + HBM_ALLOWANCE_S
 
     def result(outcome, report=None, error=""):
         return SelftestResult(
@@ -456,6 +574,10 @@ def run(
                 raise KeyError("load_mx")
             if not load_formats and "load_mx" in report:
                 raise ValueError("load_mx was not asked for")
+            if with_hbm and "hbm" not in report:
+                raise KeyError("hbm")
+            if not with_hbm and "hbm" in report:
+                raise ValueError("hbm was not asked for")
             outcome = _classify(report, load_formats)
         except (KeyError, TypeError, ValueError) as e:
             return result("error", error=f"exit {rc}, malformed report: {e!r}")
@@ -475,6 +597,8 @@ def _child(
     per_cu: bool = False,
     load_seconds: float = 0.0,
     load_formats=(),
+    hbm_seconds: float = 0.0,
+    hbm_mib: int = 0,
 ) -> Tuple[int, dict]:
     try:
         from k8s_dra_driver_amd import _hiphealth
@@ -501,6 +625,11 @@ def _child(
                         part = _hiphealth.mx_selftest(ordinal, fmt, load_seconds)
                         report["load_mx"][fmt] = part
                         report["ok"] = bool(report["ok"] and part["ok"])
+                if hbm_seconds > 0:
+                    report["hbm"] = _hiphealth.hbm_selftest(
+                        ordinal, seconds=hbm_seconds, mib=hbm_mib
+                    )
+                    report["ok"] = bool(report["ok"] and report["hbm"]["ok"])
                 return (EXIT_PASS if report["ok"] else EXIT_MISMATCH), report
         return EXIT_ERROR, {
             "ok": False,
@@ -537,6 +666,21 @@ def main(argv=None) -> int:
         + ", ".join(LOAD_FORMATS)
         + "), --load-seconds each; needs --load-seconds",
     )
+    ap.add_argument(
+        "--hbm-seconds",
+        type=float,
+        default=0.0,
+        help="as the last stage, run the HBM march (every element of the "
+        "coverage read, verified and rewritten in place, pass after pass) "
+        "for this long; 0 = off",
+    )
+    ap.add_argument(
+        "--hbm-mib",
+        type=int,
+        default=0,
+        help="memory the HBM march covers, at least 1024; 0 = all that is "
+        "free less max(2 GiB, 2 %% of the total); needs --hbm-seconds",
+    )
     ap.add_argument("--json", action="store_true", help="print the full report")
     args = ap.parse_args(argv)
     t0 = time.monotonic()
@@ -551,6 +695,16 @@ def main(argv=None) -> int:
     extra = {"load_seconds": args.load_seconds} if args.load_seconds > 0 else {}
     if formats:
         extra["load_formats"] = formats
+    if args.hbm_seconds < 0 or args.hbm_seconds > MAX_LOAD_SECONDS:
+        ap.error(f"--hbm-seconds must be in [0, {MAX_LOAD_SECONDS:g}]")
+    if args.hbm_mib and not args.hbm_seconds > 0:
+        ap.error("--hbm-mib needs a positive --hbm-seconds")
+    if args.hbm_mib < 0 or 0 < args.hbm_mib < HBM_MIN_BYTES >> 20:
+        ap.error("--hbm-mib must be 0 or at least 1024")
+    if args.hbm_seconds > 0:
+        extra["hbm_seconds"] = args.hbm_seconds
+        if args.hbm_mib:
+            extra["hbm_mib"] = args.hbm_mib
     rc, report = _child(args.bdf, args.mib, args.per_cu, **extra)
     report["seconds"] = round(time.monotonic() - t0, 3)
     if args.json:
@@ -591,6 +745,19 @@ def main(argv=None) -> int:
                 f"{part['mismatches']} mismatch(es), checksum "
                 f"{'ok' if part['checksum_ok'] else 'FAILED'}; "
                 f"{part['tflops']:.0f} TF/s (informative)"
+            )
+        if "hbm" in report:
+            hbm = report["hbm"]
+            gbs = hbm["gbs"]
+            print(
+                f"{args.bdf}: hbm march: {hbm['passes']} pass(es) over "
+                f"{hbm['bytes'] / 2**30:.1f} GiB in {hbm['chunks']} chunk(s)"
+                f"{' (allocation fell short)' if hbm['alloc_short'] else ''} "
+                f"in {hbm['seconds']:.1f}s, {hbm['mismatches']} mismatch(es) "
+                f"in {hbm['bad_pages']} 2 MiB block(s); fill "
+                f"{gbs['fill']:.0f}, march {gbs['march_addr']:.0f} / "
+                f"{gbs['march_hash']:.0f}, verify {gbs['verify']:.0f} GB/s "
+                "(informative)"
             )
     return rc
 

@@ -195,6 +195,16 @@ def main(argv=None) -> int:
         "CUs that fail; exit 1 on a mismatch",
     )
     ap.add_argument(
+        "--hbm-selftest",
+        type=float,
+        default=0.0,
+        metavar="SECONDS",
+        help="march over all free memory of every visible device (less "
+        "max(2 GiB, 2 %% of the total)) for this long: every element is "
+        "read, verified and rewritten in place, pass after pass; exit 1 on a "
+        "mismatch",
+    )
+    ap.add_argument(
         "--cu-footprint",
         action="store_true",
         help="print which compute units this process's blocks run on, per "
@@ -216,6 +226,11 @@ def main(argv=None) -> int:
         if not 0 < seconds <= MAX_LOAD_SECONDS:
             ap.error(f"--mx-selftest: SECONDS must be in (0, {MAX_LOAD_SECONDS:g}]")
         mx = (fmt, seconds)
+    if args.hbm_selftest:
+        from k8s_dra_driver_amd.selftest import MAX_LOAD_SECONDS
+
+        if not 0 < args.hbm_selftest <= MAX_LOAD_SECONDS:
+            ap.error(f"--hbm-selftest: SECONDS must be in (0, {MAX_LOAD_SECONDS:g}]")
 
     info = visible_devices()
     print(json.dumps(info))
@@ -231,6 +246,7 @@ def main(argv=None) -> int:
         or args.cu_selftest
         or args.load_selftest
         or mx
+        or args.hbm_selftest
         or args.cu_footprint
     ):
         from k8s_dra_driver_amd import _hiphealth
@@ -312,6 +328,21 @@ def main(argv=None) -> int:
                     f"checksum {'ok' if r['checksum_ok'] else 'FAILED'}, "
                     f"{r['tflops']:.0f} TF/s (informative), "
                     f"{len(r['bad_cus'])} bad CU(s)" + (f": {bad}" if bad else "")
+                )
+                if not r["ok"]:
+                    rc = 1
+            if args.hbm_selftest:
+                r = _hiphealth.hbm_selftest(d, seconds=args.hbm_selftest)
+                bad = ", ".join(f"chunk {c} block {p}" for c, p in r["bad_pages_first"])
+                print(
+                    f"device {d}: hbm-selftest {'ok' if r['ok'] else 'FAILED'}: "
+                    f"{r['passes']} pass(es) over {r['bytes'] / 2**30:.1f} GiB "
+                    f"in {r['chunks']} chunk(s)"
+                    f"{' (allocation fell short)' if r['alloc_short'] else ''} "
+                    f"in {r['seconds']:.1f}s, {r['mismatches']} mismatch(es), "
+                    f"flipped bits 0x{r['flipped_or']:016x}, march "
+                    f"{r['gbs']['march_hash']:.0f} GB/s (informative), "
+                    f"{r['bad_pages']} bad 2 MiB block(s)" + (f": {bad}" if bad else "")
                 )
                 if not r["ok"]:
                     rc = 1
